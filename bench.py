@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: purified 1 s @ 16 kHz utterances / s at 5 reverse DDPM steps (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic clips per GPU:
 q-sample -> 5 x (36 fused residual blocks + final conv + x_{t-1} update) -> M5 classify
@@ -13,12 +13,19 @@ the global utterance index, one RCCL all_gather of the [B,10] log-probabilities 
 `python bench.py --gpus N` with N > 1 and no RANK in the environment starts the N ranks itself as CHILD processes
 (`python -m torch.distributed.run ... bench.py --gpus N ...`, before anything touches a GPU) and relays rank 0's line;
 `--dry-run` does the same on CPU with the gloo backend (launcher / sharding / gather plumbing only, no kernels).
-At N = 1 the same run then times the other arithmetic modes of the path (`other_modes`: bf16, the fp32-class split mode f32s, the direct-form fp32 block),
-BASELINE configs[3] / configs[4] as their own workloads and the callers' batch shapes (`other_configs`), each with its own roofline object.
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the outputs (--dump-outputs) and
+the line.  With `--full` (off by default) and N = 1 the same run then times the other arithmetic modes of the path
+(`other_modes`: bf16, the fp32-class split mode f32s, the direct-form fp32 block), BASELINE configs[3] / configs[4] as their
+own workloads and the callers' batch shapes (`other_configs`), each with its own roofline object, samples board power
+over every leg (`power`) and times the CPU oracle (`cpu_baseline`).
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = fused residual block, timed with HIP
-events on its launch stream inside the timed region) and `cpu_baseline` (the CPU oracle on BASELINE
+events on its launch stream inside the timed region); `--full` adds `cpu_baseline` (the CPU oracle on BASELINE
 config 1, timed on this node's host cores).
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned to its caller: DIR/scores.npy, the
+gathered [global_batch, 10] log-probabilities (float32).  Inputs, weights and noise are fixed by seeds, so two runs with the
+same arguments -- of the same or of two builds -- can be compared output for output.
 """
 from __future__ import annotations
 
@@ -340,6 +347,13 @@ def scores_digest(scores):
     return {"shape": list(s.shape), "sha256": hashlib.sha256(s.numpy().tobytes()).hexdigest(), "argmax_head": s[:8].argmax(1).tolist()}
 
 
+def dump_outputs(out_dir, scores):
+    """--dump-outputs: the gathered [global_batch, K] scores of the last timed step -> out_dir/scores.npy (float32)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "scores.npy"), scores.detach().float().cpu().numpy())
+
+
 def dry_run(args) -> None:
     """CPU rehearsal of the multi-rank protocol (gloo): shard bounds, barrier, the scores all_gather, max-over-ranks
     timing, one JSON line from rank 0.  No kernel runs and `value` is not a throughput."""
@@ -370,6 +384,8 @@ def dry_run(args) -> None:
     if use_dist:
         dist.barrier()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, lp)
     ranks = rank_evidence(use_dist, el, {"index": rank, "name": "cpu (dry run)", "pci_bus_id": f"cpu:{rank}"}, "gloo")
     if use_dist:
         t = torch.tensor([el], dtype=torch.float64)
@@ -500,6 +516,11 @@ def main():
     ap.add_argument("--chunk", type=int, default=0,
                     help="clips per chain call (0 = the engine's default for the mode): the batch of a step is walked in chunks "
                          "whose activations (3 x 65.5 MB per clip) stay resident in the 256 MB Infinity Cache")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time the other modes, configs and caller shapes, sample board power and time the "
+                         "CPU baseline (N = 1; the --no-* options above trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's gathered scores to DIR/scores.npy (float32)")
     args = ap.parse_args()
 
     if args.chunk > 0 and args.batch % args.chunk:
@@ -581,7 +602,7 @@ def main():
             # (the per-launch event hook keeps small-batch chains out of their replayed graph: the callers' shapes leg times without it)
             N.check(eng.lib.ap_profile_enable(eng.ctx, 1 if profile else 0))
             fence()
-            with PowerSampler(local, enabled=rank == 0, pci_bus_id=device_descriptor(torch, local).get("pci_bus_id")) as ps:    # (rank 0's GPU only)
+            with PowerSampler(local, enabled=rank == 0 and args.full, pci_bus_id=device_descriptor(torch, local).get("pci_bus_id")) as ps:    # (rank 0's GPU only)
                 t0 = time.perf_counter()
                 for _ in range(steps):
                     lp = step()
@@ -701,13 +722,15 @@ def main():
     elapsed, k_ms, launches = run_mode(args.precision, args.steps, args.warmup)
     head_digest = scores_digest(run_mode.last_scores)
     head_scores = run_mode.last_scores.detach().float().cpu()   # the same clips and the same Philox draws run in every mode below
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head_scores)
     head_power = run_mode.power
     head_roof = roofline(args.precision, k_ms, launches)        # (now: run_mode.chunk / .split describe the run just made)
     ranks = rank_evidence(use_dist, run_mode.local_elapsed, device_descriptor(torch, local), "nccl")
-    # the other arithmetic modes of the same path, measured in the same run (N = 1 only: they are extra evidence,
+    # --full: the other arithmetic modes of the same path, measured in the same run (N = 1 only: they are extra evidence,
     # not the headline): same inputs, same chain, same timing brackets
     others = {}
-    if world == 1 and not args.no_other_modes:
+    if world == 1 and args.full and not args.no_other_modes:
         for prec in ("bf16", "bf16s", "f32s", "f32d", "f32"):
             if prec == args.precision:
                 continue
@@ -728,7 +751,7 @@ def main():
                 "max_abs_dlogp": float(f"{float((sc - head_scores).abs().max()):.3e}")}
 
     other_configs = {}
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         # BASELINE configs[3]: DiffWave VP-SDE reverse (diffwave_sde.py), n = 10, batch 512, bf16
         st = max(1, min(args.steps, 2))
         e3, k3, l3 = run_mode("bf16", st, 1, sampler="sde", n=10)
@@ -750,7 +773,7 @@ def main():
     # certified_robust.py:46-57: one-shot denoise of a batch of copies; white_box_attack.py:392,437-439: PGD through the purifier
     # at B = 10; BASELINE configs[0]: B = 2, n = 1): per-clip rate of the same path relative to the 512-clip batch
     caller_shapes = None
-    if world == 1 and not args.no_other_configs and not args.no_caller_shapes:
+    if world == 1 and args.full and not args.no_other_configs and not args.no_caller_shapes:
         from audiopure_amd.diffusion_models.diffwave_sde import RevDiffWave
         dh_ = calc_diffusion_hyperparams(**synth.DIFFUSION_CONFIG)
         ref_rate = {"f32": (world * B * args.steps / elapsed) if args.precision == "f32" else others.get("f32", {}).get("value"),
@@ -842,7 +865,7 @@ def main():
             out["other_configs"] = other_configs
         if caller_shapes:
             out.setdefault("other_configs", {})["caller_shapes"] = caller_shapes
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

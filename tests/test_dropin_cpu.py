@@ -11,14 +11,36 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 PICKLE = os.path.join(ROOT, "tests", "golden", "ref_m5_module.pt")
 
+# A stand-in for the reference checkout the *_eval.py scripts run from: its layout (top-level modules, package directories
+# without __init__.py, RCNN_KWS with one), where every module the drop-in replaces raises when imported, and the one module
+# it does not replace (robustness_eval.black_box_attack) imports its siblings relatively, as the reference's file does.
+_POISON = 'raise ImportError("the checkout\'s own {} was imported: the drop-in must shadow it")\n'
+STANDIN = {
+    "acoustic_system.py": None, "audio_models/create_model.py": None, "audio_models/M5/M5Net.py": None,
+    "audio_models/RCNN_KWS/__init__.py": None, "audio_models/RCNN_KWS/model.py": None,
+    "diffusion_models/diffwave_ddpm.py": None, "diffusion_models/diffwave_sde.py": None,
+    "diffusion_models/improved_diffusion_sde.py": None,
+    "robustness_eval/certified_robust.py": None, "robustness_eval/_NES.py": None,
+    "robustness_eval/_EOT.py": "class EOT:\n    pass\n",
+    "robustness_eval/black_box_attack.py": "from ._EOT import EOT\nfrom ._NES import NES\n",
+}
 
-def _run(code, with_reference):
-    paths = [os.path.join(ROOT, "dropin"), ROOT] + ([REF] if with_reference else [])
+
+def _standin_checkout(base):
+    for rel, text in STANDIN.items():
+        f = os.path.join(str(base), rel)
+        os.makedirs(os.path.dirname(f), exist_ok=True)
+        with open(f, "w") as fh:
+            fh.write(text if text is not None else _POISON.format(rel))
+    return str(base)
+
+
+def _run(code, checkout=None):
+    paths = [os.path.join(ROOT, "dropin"), ROOT] + ([checkout] if checkout else [])
     env = dict(os.environ, PYTHONPATH=os.pathsep.join(paths))
-    cwd = REF if with_reference else ROOT
+    cwd = checkout or ROOT
     r = subprocess.run([sys.executable, "-c", textwrap.dedent(code)], cwd=cwd, env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -59,14 +81,14 @@ SCRIPT_IMPORTS = f"""
 
 
 def test_script_imports_resolve_to_the_native_path_without_the_reference():
-    assert "OK" in _run(SCRIPT_IMPORTS, with_reference=False)
+    assert "OK" in _run(SCRIPT_IMPORTS)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout absent")
-def test_script_imports_resolve_to_the_native_path_from_inside_the_reference_checkout():
-    """cwd = the reference checkout, whose own ./audio_models/M5 create_model.py would put first on sys.path."""
+def test_script_imports_resolve_to_the_native_path_from_inside_the_reference_checkout(tmp_path):
+    """cwd = a checkout with the reference's layout (STANDIN above), whose own ./audio_models/M5 create_model.py would put first on
+    sys.path and whose replaced modules raise if they are ever imported."""
     out = _run(SCRIPT_IMPORTS + """
-    import robustness_eval.black_box_attack as bb          # the reference's own module, found through extend_path
+    import robustness_eval.black_box_attack as bb          # the checkout's own module, found through extend_path
     assert bb.NES.__module__ == "audiopure_amd.robustness_eval._NES", bb.NES.__module__
     from diffusion_models.diffwave_ddpm import DiffWave    # transfer_attack_eval.py:9
     assert DiffWave.__module__ == "audiopure_amd.diffusion_models.diffwave_ddpm"
@@ -75,7 +97,7 @@ def test_script_imports_resolve_to_the_native_path_from_inside_the_reference_che
     Classifier = KWSModel(in_size=40)                      # :74
     from diffusion_models.improved_diffusion_sde import *  # adaptive_attack_eval.py:103
     assert RevImprovedDiffusion.__module__ == "audiopure_amd.diffusion_models.improved_diffusion_sde"
-    """, with_reference=True)
+    """, checkout=_standin_checkout(tmp_path))
     assert "OK" in out
 
 

@@ -147,3 +147,33 @@ def test_config2_split_reproduces_the_single_process_digest():
         assert out["config"]["global_batch"] == 4096 and out["scores"]["shape"] == [4096, 10]
         digests[gpus] = out["scores"]["sha256"]
     assert digests[8] == digests[1] == digests[2], digests
+
+
+def test_bench_dump_outputs_writes_the_last_steps_gathered_scores(tmp_path):
+    """`--dump-outputs DIR` writes what the last timed step returned to its caller -- the gathered [global_batch, 10] scores, float32
+    -- and, the inputs being fixed by seeds, the same array for every run and every split of the same global batch over ranks
+    (CPU / gloo rehearsal through bench.py's real step function).  `--full` is an option of the command line."""
+    import hashlib
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    h = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, env=env)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout, h.stdout + h.stderr
+    got = {}
+    for tag, gpus, batch in (("a", 1, 16), ("b", 1, 16), ("c", 2, 8)):
+        d = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--dry-run", "--steps", "3", "--warmup", "1",
+                            "--batch", str(batch), "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] >= 0
+        a = np.load(d / "scores.npy")
+        assert a.shape == (16, 10) and a.dtype == np.float32 and np.isfinite(a).all()
+        assert hashlib.sha256(a.tobytes()).hexdigest() == out["scores"]["sha256"]
+        got[tag] = a
+    assert np.array_equal(got["a"], got["b"]) and np.array_equal(got["a"], got["c"])

@@ -5,8 +5,8 @@
 out=${1:-gpurun_out/r2}
 repo=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$repo/$out"; cd /tmp; export TMPDIR=/tmp
-timeout 900 python3 "$repo/bench.py" --steps 2 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --steps 1 --warmup 1 --no-cpu-baseline > "$repo/$out/stats.log" 2>&1
+timeout 900 python3 "$repo/bench.py" --full --steps 2 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline > "$repo/$out/stats.log" 2>&1
 for prec in bf16 f32; do
   for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
     n=$(echo $c | tr ' ' '_')

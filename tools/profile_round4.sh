@@ -12,8 +12,8 @@ out=${1:-gpurun_out/r4}
 repo=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p "$repo/$out"; cd /tmp; export TMPDIR=/tmp
 B=512; REPS=2
-timeout 1200 python3 "$repo/bench.py" --steps 3 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-caller-shapes > "$repo/$out/stats.log" 2>&1
+timeout 1200 python3 "$repo/bench.py" --full --steps 3 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-caller-shapes > "$repo/$out/stats.log" 2>&1
 cp "$repo/$out"/stats/*kernel_stats.csv "$repo/$out/kernel_stats.csv" 2>/dev/null
 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 "$repo/bench.py" --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs > "$repo/$out/bench_torchrun_n1.json" 2> "$repo/$out/bench_torchrun_n1.err"
 for form in ds fused; do

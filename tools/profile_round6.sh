@@ -15,8 +15,8 @@ repo=$(cd "$(dirname "$0")/.." && pwd)
 legs=${LEGS:-bench f32w bf16 f32s wb cfg4 adv}           # LEGS="bench cfg4" re-runs a subset into the same directory
 want() { case " $legs " in *" $1 "*) return 0;; esac; return 1; }
 mkdir -p "$repo/$out"; cd /tmp; export TMPDIR=/tmp
-want bench && { timeout 1500 python3 "$repo/bench.py" --steps 5 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err" ; }
-want bench && { timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --steps 1 --warmup 1 --no-cpu-baseline --no-caller-shapes > "$repo/$out/stats.log" 2>&1 ; }
+want bench && { timeout 1500 python3 "$repo/bench.py" --full --steps 5 --warmup 1 > "$repo/$out/bench.json" 2> "$repo/$out/bench.err" ; }
+want bench && { timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$repo/$out/stats" -o r -- python3 "$repo/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline --no-caller-shapes > "$repo/$out/stats.log" 2>&1 ; }
 want bench && { cp "$repo/$out"/stats/*kernel_stats.csv "$repo/$out/kernel_stats.csv" 2>/dev/null ; }
 want bench && { timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 "$repo/bench.py" --gpus 1 --steps 2 --warmup 1 --no-cpu-baseline --no-other-modes --no-other-configs > "$repo/$out/bench_torchrun_n1.json" 2> "$repo/$out/bench_torchrun_n1.err" ; }
 want f32w && { bash "$repo/tools/pmc_kernel.sh" "$out/pmc_f32w" resblock_f32w -- "$repo/tools/run_resblock.py" 512 f32 2 > "$repo/$out/pmc_f32w.log" 2>&1 ; }
