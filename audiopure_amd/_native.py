@@ -130,6 +130,18 @@ SIGNATURES = {
     "ap_axpbyc": (_i, [_fp, _fp, _fp, _f, _f, _f, _sz, _vp]),
     "ap_psample_update": (_i, [_fp, _fp, _fp, _fp, _f, _f, _f, _f, _f, _i, _sz, _vp]),
     "ap_philox_normal": (_i, [_fp, _u64, _u32, _u64, _i, _i, _vp]),
+    "ap_avg_smooth": (_i, [_fp, _fp, _i, _i, _i, _vp]),
+    "ap_median_smooth": (_i, [_fp, _fp, _vp, _i, _i, _i, _vp]),
+    "ap_median_smooth_bwd": (_i, [_fp, _vp, _fp, _i, _i, _i, _vp]),
+    "ap_at_fwd": (_i, [_fp, _fp, _fp, _f, _i, _i, _vp]),
+    "ap_at_bwd": (_i, [_fp, _fp, _fp, _fp, _f, _i, _i, _vp]),
+    "ap_ds_fwd": (_i, [_fp, _fp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _vp]),
+    "ap_ds_bwd": (_i, [_fp, _fp, C.POINTER(_f), C.POINTER(_f), _i, _i, _i, _vp]),
+    "ap_iir_scratch_elems": (_sz, [_i, _i, _i]),
+    "ap_iir_fwd": (_i, [_fp, _fp, _fp, _vp, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_double), _vp, _fp, _i, _i, _i,
+                        _vp]),
+    "ap_iir_bwd": (_i, [_fp, _fp, _vp, _fp, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_double), _vp, _fp, _i, _i, _i,
+                        _vp]),
 }
 
 _LIB = None

@@ -5,11 +5,12 @@ the whole defended forward runs in the HIP library; this class only orders the c
 
 The eval scripts build the system from a classifier they un-pickled (audio_models/create_model.py:8-17) and a torchaudio
 ``Compose`` they assembled themselves (adaptive_attack_eval.py:83-93,129-137); ``__init__`` lowers both onto the native
-modules (``audiopure_amd.lowering``), so the scripts run on the HIP path without edits."""
+modules (``audiopure_amd.lowering``), and a reference baseline defender (``TimeDomainDefense`` /
+``FreqDomainDefense``) onto ``transforms.defenses``, so the scripts run on the HIP path without edits."""
 import torch
 
 from . import _native as N
-from .lowering import lower_classifier, lower_transform
+from .lowering import lower_classifier, lower_defender, lower_transform
 
 _STAGE_OF = {"wave": 0, "spec": 1}        # where in the pipeline the defender sits
 
@@ -21,7 +22,7 @@ class AcousticSystem(torch.nn.Module):
         if defense_type not in _STAGE_OF:                                   # same refusal as acoustic_system.py:26-27
             raise NotImplementedError("argument defense_type should be 'wave' or 'spec'!")
         self.classifier, self.transform = lower_classifier(classifier), lower_transform(transform)
-        self.defender, self.defense_type = defender, defense_type
+        self.defender, self.defense_type = lower_defender(defender), defense_type
 
     def _defends_at(self, stage: int, defend) -> bool:
         # `defend == True` on purpose: the scripts pass booleans, and anything else means "no defense" there too (:35,:45)

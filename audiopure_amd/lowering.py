@@ -16,6 +16,10 @@ kws_adaptive_attack_eval.py:64-66), so "scripts unchanged" means those objects a
 * ``Sequential(MelSpectrogram(sample_rate=16000, n_mels), AmplitudeToDB('power'))`` (torchaudio defaults: n_fft 400,
   hop 200, reflect, HTK)                                                                      -> ``MelSpecDBHTK(n_mels)``
 
+* the baseline defenders ``TimeDomainDefense(t)`` / ``FreqDomainDefense(t)`` of transforms/time_defense.py /
+  transforms/frequency_defense.py (adaptive_attack_eval.py:106-125)             -> the native class, same ``defense_type``
+  (``lower_defender``; recognised by class name AND defining module, so a same-named class elsewhere is left alone)
+
 Objects that are already native are returned as they are.  Anything else is the caller's own module and is left alone
 (a mel pipeline with other parameters has no kernel here; it is not silently approximated).
 """
@@ -132,3 +136,24 @@ def lower_transform(t):
     if (sig["n_fft"], sig["hop"], sig["norm"], sig["mel_scale"], sig["pad_mode"]) == (400, 200, None, "htk", "reflect"):
         return MelSpecDBHTK(n_mels=sig["n_mels"])                            # kws_adaptive_attack_eval.py:64-66
     return t
+
+
+# class name -> the reference module that defines it (the scripts import them as `transforms.time_defense` /
+# `transforms.frequency_defense`, adaptive_attack_eval.py:14-15; a checkout imported as a package adds a prefix)
+_DEFENDERS = {"TimeDomainDefense": "transforms.time_defense", "FreqDomainDefense": "transforms.frequency_defense"}
+
+
+def lower_defender(d):
+    """A reference ``TimeDomainDefense`` / ``FreqDomainDefense`` -> the native one with the same ``defense_type``;
+    everything else (diffusion defenders, native objects, the caller's own modules, None) is returned untouched."""
+    if d is None or _is_native(d):
+        return d
+    cls = type(d)
+    mod = _DEFENDERS.get(cls.__name__)
+    if mod is None or not (cls.__module__ == mod or cls.__module__.endswith("." + mod)):
+        return d
+    defense_type = getattr(d, "defense_type", None)
+    if not isinstance(defense_type, str):
+        return d
+    from .transforms import defenses
+    return getattr(defenses, cls.__name__)(defense_type)

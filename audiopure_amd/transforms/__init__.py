@@ -1,2 +1,3 @@
 """Device-side classifier front-end transforms."""
 from .melspec import MelSpecDB, MelSpecDBHTK, ToMelSpectrogramDB  # noqa: F401
+from .defenses import AS, AT, BPF, DS, LPF, MS, FreqDomainDefense, TimeDomainDefense  # noqa: F401

@@ -433,6 +433,56 @@ int ap_psample_update(const float *x, const float *eps, const float *z, float *o
 int ap_philox_normal(float *out, uint64_t seed, uint32_t draw, uint64_t utt_offset, int B, int L,
                      void *stream);
 
+/* ---- baseline defenses (`--defense AS | MS | AT | DS | LPF | BPF`, adaptive_attack_eval.py:36,106-125) ----
+ * transforms/time_defense.py and transforms/frequency_defense.py on x[B][L], fp32, any L >= 1, 1 <= B <= 65535.  Each
+ * forward has an input-gradient launch (its adjoint); nothing reads device data on the host.  Refusals return -22 with
+ * ap_last_error set: a NULL tensor, B or L out of range, and the op-specific ones listed below. */
+#define AP_MS_MAX_WINDOW 63     /* largest median window */
+#define AP_IIR_MAX_COEF 16      /* largest len(b) == len(a) of ap_iir_*: order 15 */
+#define AP_IIR_CHUNK 128        /* time chunk of the IIR scan: AC = A^128, H[128][order] */
+#define AP_DS_DOWN_TAPS 28      /* torchaudio sinc_interpolation 16 k -> 8 k kernel (width 13, stride 2) */
+#define AP_DS_UP_TAPS 15        /* ... 8 k -> 16 k kernel per output phase (width 7, 2 phases) */
+
+/* AS (time_defense.py:117-124): y[n] = sum_{|j| <= r} w x[n + j], k = 2r + 1, w = float(1 / k), zero padding.
+ * The operator is symmetric Toeplitz: its adjoint IS this launch (call it on the cotangent).  Refuses an even or
+ * non-positive k. */
+int ap_avg_smooth(const float *x, float *y, int k, int B, int L, void *stream);
+/* MS (time_defense.py:146-156): y[n] = median of x[n - r .. n + r] (zero padding, odd k <= AP_MS_MAX_WINDOW); argoff[n]
+ * (int8, in [-r, r]) is the offset of the element picked.  Tie rule: the element of rank r in the order (value, then
+ * position), i.e. the middle one of a run of equal values in window order.  Refuses an even k or k > 63. */
+int ap_median_smooth(const float *x, float *y, int8_t *argoff, int k, int B, int L, void *stream);
+/* MS adjoint, a gather with no atomics: dx[m] = sum over n with n + argoff[n] == m of g[n] (n ascending). */
+int ap_median_smooth_bwd(const float *g, const int8_t *argoff, float *dx, int k, int B, int L, void *stream);
+/* AT (time_defense.py:93-100): P = sum_n x^2 / L per clip, y = x + z sqrt(P / snr), snr = 10^(param / 10); z [B][L] is
+ * given (the Python layer fills it from ap_philox_normal unless the caller injects it).  A silent clip (P = 0) gives y = x.
+ * Refuses snr <= 0. */
+int ap_at_fwd(const float *x, const float *z, float *y, float snr, int B, int L, void *stream);
+/* AT adjoint, with the term through P as autograd differentiates the reference: dx = g + (sum g z) x / (L snr sqrt(P / snr));
+ * for a silent clip that term is dropped (dx = g; the reference's autograd gives NaN there). */
+int ap_at_bwd(const float *x, const float *z, const float *g, float *dx, float snr, int B, int L, void *stream);
+/* DS (frequency_defense.py:38-58): torchaudio 0.11 Resample(16 k -> 8 k) then Resample(8 k -> 16 k), sinc_interpolation,
+ * lowpass_filter_width 6, rolloff 0.99.  kd[28] and ku[2][15] (HOST arrays, fp32) are the two kernels as torchaudio
+ * builds them; d[m] = sum_j kd[j] x[2m + j - 13] for 0 <= m < M = ceil(L / 2), y[2n + p] = sum_j ku[p][j] d[n + j - 7];
+ * y is [B][Lout] with Lout = L (same_size) or 2M.  Refuses any other Lout. */
+int ap_ds_fwd(const float *x, float *y, const float *kd, const float *ku, int B, int L, int Lout, void *stream);
+/* DS adjoint: g [B][Lout] -> dx [B][L], the transposed up- then down-sampling pair. */
+int ap_ds_bwd(const float *g, float *dx, const float *kd, const float *ku, int B, int L, int Lout, void *stream);
+/* LPF / BPF (frequency_defense.py:60-141): lfilter(b, a) per clip (direct form II transposed, zero initial state), then
+ * clamp.  b, a: HOST arrays of ncoef (2 .. AP_IIR_MAX_COEF) fp32 coefficients, normalised here by a[0]; AC: HOST fp64
+ * [N][N] (N = ncoef - 1) = A^AP_IIR_CHUNK of the state recurrence s' = A s + B u, A[i][0] = -a[i+1], A[i][i+1] = 1; H:
+ * DEVICE fp64 [AP_IIR_CHUNK][N], H[k] = e_0' A^k (the zero-input output basis).  The state is carried in fp64 (poles near
+ * the unit circle amplify fp32 state rounding); input and output are fp32.  scratch: ap_iir_scratch_elems floats.
+ * Clamp rule over the whole batch, decided on the device (minmax: 2 DEVICE words this call writes): [-1, 1] if
+ * 0.9 max(x) <= 1 and 0.9 min(x) >= -1, else [-2^(bits-1), 2^(bits-1) - 1].  ypre (may be NULL) receives the values
+ * before the clamp.  Refuses ncoef outside 2 .. 16, a[0] == 0, bits outside 2 .. 31. */
+size_t ap_iir_scratch_elems(int ncoef, int B, int L);
+int ap_iir_fwd(const float *x, float *y, float *ypre, unsigned *minmax, const float *b, const float *a, int ncoef,
+               const double *AC, const double *H, float *scratch, int bits, int B, int L, void *stream);
+/* LPF / BPF adjoint: the same scan backwards in time on g * 1[lo <= ypre <= hi] (inclusive, as clamp's backward), with the
+ * forward's ypre and minmax; ypre == NULL applies no mask (the adjoint of the filter alone). */
+int ap_iir_bwd(const float *g, const float *ypre, const unsigned *minmax, float *dx, const float *b, const float *a,
+               int ncoef, const double *AC, const double *H, float *scratch, int bits, int B, int L, void *stream);
+
 /* ---- keyword-spotting route: clips of any length ----
  * ap_kws_*: KWSModel.forward (audio_models/RCNN_KWS/model.py:66-114): depthwise Conv1d(k=5, s=2) + grouped pointwise
  * Conv1d(s=8), 2-layer bidirectional GRU, additive attention, linear, log-softmax.  `blob_dev`: the state dict
