@@ -142,6 +142,9 @@ SIGNATURES = {
                         _vp]),
     "ap_iir_bwd": (_i, [_fp, _fp, _vp, _fp, C.POINTER(_f), C.POINTER(_f), _i, C.POINTER(C.c_double), _vp, _fp, _i, _i, _i,
                         _vp]),
+    "ap_psy_scratch_elems": (_sz, [_i, _i, _i, _i]),
+    "ap_psy_threshold": (_i, [_fp, _vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "ap_psy_loss_grad": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
 }
 
 _LIB = None

@@ -5,6 +5,7 @@
 #include <math.h>
 
 #include "ap_common.h"
+#include "ap_fft.h"
 
 namespace ap {
 
@@ -13,28 +14,6 @@ constexpr int NFFT = 2048, HOP = 512, NBIN = NFFT / 2 + 1, MAX_MELS = 128;
 struct MelPts {
   float f[MAX_MELS + 2];   // filter corner frequencies in Hz (n_mels + 2 used)
 };
-
-// forward 2048-point Stockham radix-2 FFT in LDS (all 256 threads); returns the buffer holding the result
-__device__ __forceinline__ float2 *fft2048(float2 *bufA, float2 *bufB, const float2 *tw, int tid) {
-  float2 *src = bufA, *dst = bufB;
-#pragma unroll 1
-  for (int Ns = 1; Ns < NFFT; Ns <<= 1) {
-    const int tstride = (NFFT / 2) / Ns;
-    for (int jj = tid; jj < NFFT / 2; jj += 256) {
-      const int k = jj & (Ns - 1);
-      const float2 w = tw[k * tstride];
-      const float2 a = src[jj];
-      const float2 c = src[jj + NFFT / 2];
-      const float2 bw = make_float2(c.x * w.x - c.y * w.y, c.x * w.y + c.y * w.x);
-      const int o = ((jj - k) << 1) + k;
-      dst[o] = make_float2(a.x + bw.x, a.y + bw.y);
-      dst[o + Ns] = make_float2(a.x - bw.x, a.y - bw.y);
-    }
-    __syncthreads();
-    float2 *t = src; src = dst; dst = t;
-  }
-  return src;
-}
 
 __global__ __launch_bounds__(256) void melspec_kernel(const float *__restrict__ x, float *__restrict__ out, MelPts pts,
                                                       int n_mels, int n_frames, int L) {

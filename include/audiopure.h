@@ -483,6 +483,26 @@ int ap_iir_fwd(const float *x, float *y, float *ypre, unsigned *minmax, const fl
 int ap_iir_bwd(const float *g, const float *ypre, const unsigned *minmax, float *dx, const float *b, const float *a,
                int ncoef, const double *AC, const double *H, float *scratch, int bits, int B, int L, void *stream);
 
+/* ---- psychoacoustic masking threshold and hinge loss of the attack's second, imperceptible stage (Qin et al. 2019;
+ * robustness_eval/white_box_attack.py:36-273 PsychoacousticMasker, :610-710 AudioAttack's loss, gradient and stabilised
+ * thresholds).  Window 2048 (periodic Hann), hop `hop`, center=False: F = 1 + (L - 2048) / hop frames of 1025 bins.
+ * `tables`: DEVICE fp64 [AP_PSY_TABLE_ELEMS] built on the host from the masker's sample rate: the analysis window
+ * (scipy.signal.get_window("hann", 2048), :163-168) at 0, the bark scale of the 1025 bin frequencies at 2048 (:111-125),
+ * the absolute threshold of hearing at 3073 (-inf outside 20 Hz .. 20 kHz; :127-149).  `scratch`: ap_psy_scratch_elems
+ * floats, shared by both calls.  Window sizes other than 2048, hop outside [1, 2048] and L < 2048 are refused (-22). */
+#define AP_PSY_TABLE_ELEMS (2048 + 2 * 1025)
+size_t ap_psy_scratch_elems(int window, int hop, int B, int L);
+/* PsychoacousticMasker.calculate_threshold_and_psd_maximum (:61-86) for x [B][L] plus the stabilisation of
+ * AudioAttack._stabilized_threshold_and_psd_maximum (:692-715): thr_stab [B][1025][F] = 10^(0.1 threshold),
+ * psd_max_stab [B] = 10^(0.1 psd_max).  thr_db [B][1025][F] (the fp32 threshold in dB) and psd_max_db [B] may be NULL. */
+int ap_psy_threshold(const float *x, const double *tables, float *thr_stab, float *thr_db, float *psd_max_stab,
+                     float *psd_max_db, float *scratch, int window, int hop, int B, int L, void *stream);
+/* AudioAttack._loss_gradient_masking_threshold (:610-690) for the perturbation delta [B][L]: loss [B] = mean over bins and
+ * frames of relu(10^9.6 / psd_max_stab |sqrt(8/3) STFT(delta) / 2048|^2 - thr_stab), grad [B][L] = dloss[b] / ddelta[b]
+ * (0 past the last frame; 0 where the spectrum is exactly 0, where the reference's sqrt backward gives NaN). */
+int ap_psy_loss_grad(const float *delta, const float *thr_stab, const float *psd_max_stab, float *grad, float *loss,
+                     float *scratch, int window, int hop, int B, int L, void *stream);
+
 /* ---- keyword-spotting route: clips of any length ----
  * ap_kws_*: KWSModel.forward (audio_models/RCNN_KWS/model.py:66-114): depthwise Conv1d(k=5, s=2) + grouped pointwise
  * Conv1d(s=8), 2-layer bidirectional GRU, additive attention, linear, log-softmax.  `blob_dev`: the state dict

@@ -1,0 +1,162 @@
+"""Stage 2 of the white-box attack without a GPU: the restatement (tests/psy_restate.py) against the reference's recorded
+thresholds, PSD maxima, losses and gradients (tests/golden/golden_psy_v1.npz), the host-built tables bit for bit, the
+drop-in ``robustness_eval.white_box_attack`` through a stand-in checkout, and the refusals."""
+import ctypes
+import os
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import psy_restate as R  # noqa: E402
+from audiopure_amd import _native as N  # noqa: E402
+from audiopure_amd.robustness_eval import psychoacoustic as P  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLIPS = ("noise", "tones", "silent", "hop256", "sr44k")
+
+
+@pytest.fixture(scope="module")
+def G():
+    return np.load(os.path.join(ROOT, "tests", "golden", "golden_psy_v1.npz"))
+
+
+@pytest.mark.parametrize("name", CLIPS)
+def test_restated_threshold_equals_the_reference(G, name):
+    thr, pmax = R.threshold(G[f"thr/{name}/x"], int(G[f"thr/{name}/hop"]), int(G[f"thr/{name}/sr"]))
+    assert thr.dtype == np.float32 and np.array_equal(thr, G[f"thr/{name}/db"])
+    assert pmax == G[f"thr/{name}/psd_max"]
+    if name == "silent":                       # all-zero frames: no maskers, -inf below 20 Hz (stabilised 0)
+        assert np.isneginf(thr[:3, 4:10]).all() and np.isfinite(thr[3:]).all()
+
+
+def test_restated_loss_and_grad_equal_the_reference_along_its_trajectory(G):
+    for i in range(G["traj/delta"].shape[0]):
+        loss, grad = R.loss_and_grad(G["traj/delta"][i], G["traj/thr_stab"], G["traj/psd_max_stab"])
+        assert np.abs(loss / G["traj/loss"][i] - 1).max() <= 1e-6
+        want = G["traj/grad"][i][:, 0]
+        for b in range(want.shape[0]):
+            assert np.abs(grad[b] - want[b]).max() <= 1e-5 * np.abs(want[b]).max()
+
+
+def test_host_tables_equal_the_reference_bit_for_bit(G):
+    assert np.array_equal(P.hann_periodic(2048), G["window"])
+    for sr in (16000, 44100):
+        m = P.PsychoacousticMasker(sample_rate=sr)
+        assert np.array_equal(m.bark, G[f"bark/{sr}"])
+        assert np.array_equal(m.absolute_threshold_hearing, G[f"ath/{sr}"])
+    m = P.PsychoacousticMasker(hop_size=256, sample_rate=22050)
+    assert (m.window_size, m.hop_size, m.sample_rate) == (2048, 256, 22050)
+    assert m.fft_frequencies.shape == (1025,) and m.fft_frequencies[-1] == 11025.0
+
+
+def test_refusals_raise_before_any_launch():
+    with pytest.raises(ValueError, match="window_size 4096"):
+        P.PsychoacousticMasker(window_size=4096)
+    m = P.PsychoacousticMasker()
+    with pytest.raises(ValueError, match="shorter than one window"):
+        m.threshold_and_psd_maximum(torch.zeros(2, 1, 2047))
+    with pytest.raises(ValueError, match="shorter than one window"):
+        P.masking_threshold_loss_and_grad(torch.zeros(2, 1, 2000), torch.zeros(2, 1025, 1), torch.ones(2))
+    with pytest.raises(N.NativeError, match="CPU"):
+        m.threshold_and_psd_maximum(torch.zeros(2, 1, 4096))
+    lib = N.lib()
+    assert lib.ap_psy_scratch_elems(4096, 512, 1, 16000) == 0
+    assert lib.ap_psy_scratch_elems(2048, 512, 3, 16000) == 3 * 28 * 2049
+    fake = ctypes.c_void_p(16)                 # never dereferenced: the shape checks come first
+    for window, hop, L in ((4096, 512, 16000), (2048, 512, 2047), (2048, 0, 16000)):
+        assert lib.ap_psy_threshold(fake, fake, fake, None, fake, None, fake, window, hop, 1, L, None) == -22
+        assert lib.ap_psy_loss_grad(fake, fake, fake, fake, fake, fake, window, hop, 1, L, None) == -22
+    assert lib.ap_psy_threshold(fake, fake, fake, None, fake, None, fake, 4096, 512, 1, 16000, None) == -22
+    assert b"window_size 4096" in lib.ap_last_error()
+
+
+# A stand-in reference checkout: its white_box_attack.py has the reference's layout (a relative import of _EOT, an
+# AudioAttack with the two stage-2 hooks) and a PsychoacousticMasker that raises if it is ever used.
+STANDIN_WBA = '''
+from ._EOT import EOT
+
+
+def project_to_norm_ball(x, p, eps):
+    return "checkout"
+
+
+def lp_norm(x, p):
+    return "checkout"
+
+
+class PsychoacousticMasker:
+    def __init__(self, *a, **k):
+        raise RuntimeError("the checkout's PsychoacousticMasker was used")
+
+
+class AudioAttack:
+    def __init__(self, model, masker=None, **kw):
+        self.model, self.masker = model, masker
+
+    def generate(self, x, y, targeted=True):
+        return self.stage_1(x, y)
+
+    def stage_1(self, x, y):
+        return "stage_1 of the checkout"
+
+    def stage_2(self, x, x_adv, y=None):
+        return "stage_2 of the checkout"
+
+    def _loss_gradient_masking_threshold(self, perturbation, x, masking_threshold_stabilized, psd_maximum_stabilized):
+        raise RuntimeError("the checkout's hinge loss was used")
+
+    def _stabilized_threshold_and_psd_maximum(self, x):
+        raise RuntimeError("the checkout's threshold was used")
+'''
+
+
+def _run(code, checkout=None):
+    paths = [os.path.join(ROOT, "dropin"), ROOT] + ([checkout] if checkout else [])
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join(paths))
+    r = subprocess.run([sys.executable, "-c", textwrap.dedent(code)], cwd=checkout or ROOT, env=env, capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r.stdout
+
+
+def test_dropin_white_box_attack_dispatches_the_two_hooks_and_keeps_the_rest(tmp_path):
+    os.makedirs(tmp_path / "robustness_eval")
+    (tmp_path / "robustness_eval" / "_EOT.py").write_text("class EOT:\n    pass\n")
+    (tmp_path / "robustness_eval" / "white_box_attack.py").write_text(STANDIN_WBA)
+    out = _run("""
+        from robustness_eval.white_box_attack import *
+        import robustness_eval.white_box_attack as wba
+        import os, sys
+        from audiopure_amd.robustness_eval import psychoacoustic
+        ref = sys.modules["robustness_eval._checkout_white_box_attack"]
+        assert wba.__file__.endswith(os.path.join("dropin", "robustness_eval", "white_box_attack.py")), wba.__file__
+        assert PsychoacousticMasker is psychoacoustic.PsychoacousticMasker
+        assert issubclass(AudioAttack, ref.AudioAttack) and AudioAttack is not ref.AudioAttack
+        own = {k for k, v in vars(AudioAttack).items() if callable(v)}
+        assert own == {"_stabilized_threshold_and_psd_maximum", "_loss_gradient_masking_threshold"}, own
+        for name in ("stage_1", "stage_2", "generate"):
+            assert getattr(AudioAttack, name) is getattr(ref.AudioAttack, name), name
+        assert project_to_norm_ball(None, "linf", 1) == "checkout" and lp_norm(None, "linf") == "checkout"
+        assert sys.modules["robustness_eval._EOT"].__file__.startswith(os.getcwd())      # the checkout's own _EOT
+        assert EOT.__module__ == "robustness_eval._EOT"
+        attack = AudioAttack(model=None, masker=PsychoacousticMasker(hop_size=256))
+        assert attack.generate(None, None) == "stage_1 of the checkout"
+        print("OK")
+        """, checkout=str(tmp_path))
+    assert "OK" in out
+
+
+def test_dropin_white_box_attack_without_a_checkout_names_what_is_missing():
+    out = _run("""
+        try:
+            import robustness_eval.white_box_attack
+        except ImportError as e:
+            assert "white_box_attack.py" in str(e) and "audiopure_amd.robustness_eval.psychoacoustic" in str(e), e
+            print("OK")
+        """)
+    assert "OK" in out
