@@ -341,7 +341,10 @@ extern "C" int ap_ctx_load_wavenet(ap_ctx *ctx, const float *blob_dev, size_t n_
 extern "C" int ap_ctx_prepare_backward(ap_ctx *ctx, void *stream) {
   if (!ctx || !ctx->loaded) { set_error("ap_ctx_prepare_backward: weights not loaded (ap_ctx_load_wavenet)"); return -22; }
   if (ctx->bwd_ready) return 0;
-  if (ctx->C != 256 || ctx->S != 256) { set_error("ap_ctx_prepare_backward: the fused backward kernels are built for res = skip = 256 channels"); return -22; }
+  if (ctx->C != 256 || ctx->S != 256) {
+    set_error("ap_ctx_prepare_backward: the fused backward kernels are built for AP_PREC_F32, AP_PREC_BF16 and AP_PREC_BF16_STORE with res = skip = 256 channels");
+    return -22;
+  }
   if (ctx->cfg.precision == AP_PREC_F32) return prepare_bwd_f32(ctx, (hipStream_t)stream);
   if (ctx->cfg.precision == AP_PREC_BF16 || ctx->cfg.precision == AP_PREC_BF16_STORE) return prepare_bwd_bf16(ctx, (hipStream_t)stream);
   set_error("ap_ctx_prepare_backward: no fused backward in precision %d (AP_PREC_F32, AP_PREC_BF16, AP_PREC_BF16_STORE)", ctx->cfg.precision);

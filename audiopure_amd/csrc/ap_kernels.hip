@@ -548,11 +548,12 @@ static int g_ablate = 0;       // timing-only ablation mask (ap_debug_ablate)
 int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
                     int accumulate, int B, int L, hipStream_t st, float *aout, const UbArgs *ub, void *gout, void *fout) {
   if (aout && ctx->cfg.precision != AP_PREC_F32) {
-    set_error("ap_resblock_fwd_save: fp32 arithmetic only (the other modes recompute the pre-gate activations)");
+    set_error("ap_resblock_fwd_save: AP_PREC_F32 only (the other modes recompute the pre-gate activations)");
     return -22;
   }
   if (ctx->cfg.precision == AP_PREC_BF16_STORE) {
-    set_error("AP_PREC_BF16_STORE: the residual stream is a bf16 image in this mode (ap_init_conv_u / ap_resblock_fwd_u), not an fp32 tensor");
+    set_error("AP_PREC_BF16_STORE: the residual stream is a bf16 image in this mode (ap_init_conv_u / ap_resblock_fwd_u), not an fp32 tensor; "
+              "the fp32-tensor block serves AP_PREC_F32, AP_PREC_F32_SPLIT and AP_PREC_BF16");
     return -22;
   }
   if (gout && (ctx->cfg.precision != AP_PREC_BF16 || g_force_f32)) {

@@ -594,16 +594,25 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_conv_bf16_kernel(const __
     }
 }
 
-bool resblock_bwd_bf16_serves(const ap_ctx *ctx, int B, int L) {
+// the backward from kept gate factors (ap_resblock_bwd_bf16_saved): both bf16 modes -- the factor image has one layout in both
+bool resblock_bwd_bf16_saved_serves(const ap_ctx *ctx, int B, int L) {
   if ((ctx->cfg.precision != AP_PREC_BF16 && ctx->cfg.precision != AP_PREC_BF16_STORE) || ctx->C != QC_ || ctx->S != QC_ || !ctx->loaded) return false;
   if ((size_t)2 * QC_ * (size_t)L * 4 >= ((size_t)1 << 31)) return false;
   return (long long)B * ((L + 63) / 64) < (1ll << 31);
 }
 
+// the recomputing backward (ap_resblock_bwd_bf16): AP_PREC_BF16 only.  Its gate kernel stages h_in + part_t in natural channel order
+// against the forward's GEMM1 image, which AP_PREC_BF16_STORE packs with a permuted K order (the u image's row order)
+bool resblock_bwd_bf16_serves(const ap_ctx *ctx, int B, int L) {
+  return ctx->cfg.precision == AP_PREC_BF16 && resblock_bwd_bf16_saved_serves(ctx, B, L);
+}
+
 int launch_resblock_bwd_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, const float *dhp, const float *dskip, void *dy,
                              float *dhin, int B, int L, hipStream_t st) {
   if (!resblock_bwd_bf16_serves(ctx, B, L)) {
-    set_error("ap_resblock_bwd_bf16: built for AP_PREC_BF16 with res = skip = 256 channels and clips below 2^20 samples");
+    set_error(ctx->cfg.precision == AP_PREC_BF16_STORE
+                  ? "ap_resblock_bwd_bf16: built for AP_PREC_BF16 only; AP_PREC_BF16_STORE contexts take ap_resblock_bwd_bf16_saved"
+                  : "ap_resblock_bwd_bf16: built for AP_PREC_BF16 with res = skip = 256 channels and clips below 2^20 samples");
     return -22;
   }
   if (!ctx->bwd_ready) {                                         // (launch functions allocate nothing: include/audiopure.h)
@@ -653,8 +662,8 @@ int launch_rows_image_bf16(const float *x, void *img, int B, int L, hipStream_t 
 // dskip_is_image: dskip is the bf16 image [B][L][S] of ap_bwd_bf16_rows_image instead of fp32 rows [B][S][L]
 int launch_resblock_bwd_bf16_saved(ap_ctx *ctx, int layer, const void *fac, const float *dhp, const void *dskip, int dskip_is_image, void *dy,
                                    float *dhin, int B, int L, hipStream_t st) {
-  if (!resblock_bwd_bf16_serves(ctx, B, L)) {
-    set_error("ap_resblock_bwd_bf16_saved: built for AP_PREC_BF16 with res = skip = 256 channels and clips below 2^20 samples");
+  if (!resblock_bwd_bf16_saved_serves(ctx, B, L)) {
+    set_error("ap_resblock_bwd_bf16_saved: built for AP_PREC_BF16 / AP_PREC_BF16_STORE with res = skip = 256 channels and clips below 2^20 samples");
     return -22;
   }
   if (!ctx->bwd_ready) {
@@ -717,7 +726,7 @@ extern "C" int ap_resblock_bwd_bf16_saved(ap_ctx *ctx, int layer, const void *ga
   return ap::launch_resblock_bwd_bf16_saved(ctx, layer, gate_factors, dh_out, dskip, dskip_is_image, dy_scratch, dh_in, B, L, (hipStream_t)stream);
 }
 
-extern "C" int ap_resblock_bwd_bf16_available(ap_ctx *ctx, int B, int L) { return ctx && ap::resblock_bwd_bf16_serves(ctx, B, L) ? 1 : 0; }
+extern "C" int ap_resblock_bwd_bf16_available(ap_ctx *ctx, int B, int L) { return ctx && ap::resblock_bwd_bf16_saved_serves(ctx, B, L) ? 1 : 0; }
 
 #ifdef AP_TOOLS
 extern "C" int ap_debug_bwdb_linear(int v) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(ap::g_bwdb_linear), &v, sizeof(v)); }

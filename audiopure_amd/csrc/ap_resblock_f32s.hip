@@ -463,7 +463,9 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
         mma2(p1, ks + 2);
         __builtin_amdgcn_sched_barrier(0);
       }
-      const float addm = (pass == 0 || accumulate) ? 1.0f : 0.0f;
+      // pass 0 adds the residual u, pass 1 the old skip when accumulating; otherwise the old skip is not an operand at all (a 0 x pre
+      // product would turn NaN / Inf bits of an unwritten buffer into the written value)
+      const bool add = pass == 0 || accumulate;
       const float scale = pass == 0 ? RS : 1.0f;
 #pragma unroll
       for (int c2 = 0; c2 < 2; c2++) {
@@ -474,10 +476,10 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
           for (int p = 0; p < 4; p++) {
             const float4 v = *reinterpret_cast<const float4 *>(patch + ((lane >> 3) + 8 * p) * PSTR + 4 * (lane & 7));
             f32x4 o;
-            o[0] = __builtin_fmaf(pre[c2][4 * p + 0], addm, v.x) * scale;
-            o[1] = __builtin_fmaf(pre[c2][4 * p + 1], addm, v.y) * scale;
-            o[2] = __builtin_fmaf(pre[c2][4 * p + 2], addm, v.z) * scale;
-            o[3] = __builtin_fmaf(pre[c2][4 * p + 3], addm, v.w) * scale;
+            o[0] = (add ? pre[c2][4 * p + 0] + v.x : v.x) * scale;
+            o[1] = (add ? pre[c2][4 * p + 1] + v.y : v.y) * scale;
+            o[2] = (add ? pre[c2][4 * p + 2] + v.z : v.z) * scale;
+            o[3] = (add ? pre[c2][4 * p + 3] + v.w : v.w) * scale;
             // offset in the VGPR, soffset = 0 (a >8-byte buffer store with an SGPR soffset reads its data late)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), pass == 0 ? ors : srs,
                                                    evoff[c2] + (unsigned)(8 * p * L * 4), 0, 2);
@@ -486,7 +488,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
 #pragma unroll
           for (int r = 0; r < 16; r++)
             __builtin_amdgcn_raw_buffer_store_b32(
-                __builtin_bit_cast(unsigned, __builtin_fmaf(pre[c2][r], addm, ac[c2][r]) * scale), pass == 0 ? ors : srs,
+                __builtin_bit_cast(unsigned, (add ? pre[c2][r] + ac[c2][r] : ac[c2][r]) * scale), pass == 0 ? ors : srs,
                 evoff[c2], ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
         }
       }

@@ -106,29 +106,31 @@ class EpsGrad:
         N.check(lib.ap_conv2d_fwd(N.ptr(x), N.ptr(packed), N.ptr(bias), N.ptr(res), N.ptr(out), B, Cin, 1, L, Cout, 1, kw, 1,
                                   pad, 1, fl, Cin, 0, N.stream()), "ap_conv2d_fwd")
 
-    def saved_bytes(self, x: torch.Tensor, acts: bool = True) -> int:
+    def saved_bytes(self, x: torch.Tensor, acts: bool = True, split: bool = False):
         """Bytes ``forward_save(x, ., acts)`` keeps, computed without allocating: NL + 1 layer inputs [B][C][L], the skip sum,
         the FiLM vectors and -- ``acts`` in fp32 arithmetic -- NL pre-gate tensors [B][2C][L]; in bf16 mode also the gate-image
         buffer of the deferred-skip forward while this object does not hold one of that size yet (it is allocated once and
-        reused by every link, so only the first link is charged for it)."""
+        reused by every link, so only the first link is charged for it).  ``split``: the pair (bytes the link keeps, bytes of
+        that one-off buffer) instead of their sum."""
         eng = self._prepare()
         B, _, L = x.shape
         C_, S_, NL = self.C, self.S, self.NL
         bstore = self.net._precision == N.AP_PREC_BF16_STORE
         keeps = bstore or (acts and self._keeps_factors(eng, B, L))
-        # (kept factors: layer 0's input + a ping-pong pair -- a pair of bf16 u images, half the bytes, with bf16 storage)
-        n = ((2 if bstore else 3) if keeps else NL + 1) * B * C_ * L + B * S_ * L + NL * C_ + eng.cfg.embed_dim_out
+        # (kept factors: layer 0's input + a ping-pong pair; with bf16 storage layer 0's input only -- the u images are the sweep's own)
+        n = ((1 if bstore else 3) if keeps else NL + 1) * B * C_ * L + B * S_ * L + NL * C_ + eng.cfg.embed_dim_out
         if acts and self.net._precision == N.AP_PREC_F32 and C_ in (64, 256):
             n += NL * B * 2 * C_ * L
         extra = 0
         if keeps:
             extra += NL * int(eng.lib.ap_gate_factor_bytes(B, L))
+        once = 0
         G = self._group(eng)
         if G > 0:
             need = min(G, NL) * B * L * C_ * 2
             if self._gimg is None or self._gimg.numel() * 2 < need or self._gimg.device != x.device:
-                extra = need
-        return 4 * n + extra
+                once = need
+        return (4 * n + extra, once) if split else 4 * n + extra + once
 
     def _keeps_factors(self, eng, B, L) -> bool:
         """bf16 mode at the shipped shape: the forward pass keeps the gate's derivative factors (ap_resblock_fwd_gate_save: 16.4 MB per
@@ -387,8 +389,11 @@ class _ChainFn(torch.autograd.Function):
                 cur = _axpby(cur, None, qa, 0.0)
             budget = _chain_budget(cur.device)
             sizes = getattr(grad, "saved_bytes", None)           # analytic sizes where the gradient object knows them: nothing is
-            full = sizes(cur, True) if sizes else None           # allocated to find out that it does not fit
-            lean = sizes(cur, False) if sizes else None
+            full = lean = None                                   # allocated to find out that it does not fit
+            once = 0                                             # (a buffer the first saving link allocates and every later one reuses)
+            if sizes:
+                full, once = sizes(cur, True, split=True)
+                lean, _ = sizes(cur, False, split=True)
             for (t, ca, cb, cs, draw) in steps:
                 xs.append(cur)
                 if full is None:                                 # (a gradient object without sizes: measure its first link)
@@ -400,13 +405,15 @@ class _ChainFn(torch.autograd.Function):
                     if saved is not None:
                         held += _saved_bytes(saved)
                     saves.append(saved)
-                elif held + full <= budget:
+                elif held + once + full <= budget:
                     eps, saved = grad.forward_save(cur, t)
-                    held += full
+                    held += once + full
+                    once = 0
                     saves.append(saved)
-                elif lean < full and held + lean <= budget:
+                elif lean < full and held + once + lean <= budget:
                     eps, saved = grad.forward_save(cur, t, acts=False)    # layer inputs only: the backward recomputes the dilated conv
-                    held += lean
+                    held += once + lean
+                    once = 0
                     saves.append(saved)
                 else:
                     eps = eps_only(cur, t) if eps_only is not None else grad.forward_save(cur, t)[0]

@@ -167,14 +167,16 @@ size_t ap_workspace_bytes(const ap_ctx *ctx, int B, int L);
  *   floats: [num_res_layers][C] FiLM vectors, then the shared 512-d embedding (scratch). */
 int ap_embed(ap_ctx *ctx, float step, float *part_t_dev, void *stream);
 
-/* ap_init_conv: ReLU(Conv1x1 1->C) (WaveNet.py:147,168).  x [B][1][L] -> h [B][C][L]. */
+/* ap_init_conv: ReLU(Conv1x1 1->C) (WaveNet.py:147,168).  x [B][1][L] -> h [B][C][L].  Every precision mode and width: an fp32
+ * primitive (in AP_PREC_BF16_STORE it forms the fp32 h_0 that the input gradient's ap_init_conv_bwd reads). */
 int ap_init_conv(ap_ctx *ctx, const float *x, float *h, int B, int L, void *stream);
 
 /* ap_resblock_fwd: one Residual_block.forward (WaveNet.py:75-97), fused:
  *   u = h_in + part_t[c]; y = DilConv_{k=3,d}(u) + b; g = tanh(y[:C]) * sigmoid(y[C:]);
  *   h_out = (u + W_res g + b_res) * sqrt(.5); skip (+)= W_skip g + b_skip.
  * part_t_layer: [C] for this layer.  accumulate_skip = 0 writes skip (layer 0), else adds.
- * h_out must not alias h_in (taps at t +- d read other tiles). */
+ * h_out must not alias h_in (taps at t +- d read other tiles).  Serves AP_PREC_F32 (res_channels 64, 128 or 256), AP_PREC_F32_SPLIT
+ * and AP_PREC_BF16 (res = skip = 256); -22 in AP_PREC_BF16_STORE (below). */
 int ap_resblock_fwd(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer,
                     float *h_out, float *skip, int accumulate_skip, int B, int L, void *stream);
 
@@ -192,7 +194,9 @@ int ap_resblock_fwd(ap_ctx *ctx, int layer, const float *h_in, const float *part
  * Results: h identical bit for bit; skip differs from the per-layer form by fp32 summation order only (the bf16 products are
  * the same; a group's K = G x 256 is accumulated in the matrix pipe's fp32 accumulators).
  * ap_resblock_fwd_gate launches of at most one 128-sample tile per CU (one or two 1 s clips) run on 64-sample tiles
- * (ap_resblock_bf16s.hip) with bit-identical results: a clip's h' and g image do not depend on the batch it travels in. */
+ * (ap_resblock_bf16s.hip) with bit-identical results: a clip's h' and g image do not depend on the batch it travels in.
+ * ap_resblock_fwd_gate: AP_PREC_BF16 only.  ap_skip_gemm and ap_ctx_set_skip_group(G > 0): AP_PREC_BF16 and AP_PREC_BF16_STORE,
+ * res = skip = 256 channels; -22 in every other mode (ap_ctx_set_skip_group(0) is accepted everywhere). */
 int ap_resblock_fwd_gate(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
                          void *g_image, int B, int L, void *stream);
 int ap_skip_gemm(ap_ctx *ctx, int layer0, int n_layers, const void *g_images, float *skip, int accumulate_skip,
@@ -208,7 +212,9 @@ int ap_ctx_set_skip_group(ap_ctx *ctx, int layers_per_group);
  *                      u_out NULL (the net's last layer, whose h' nobody reads: WaveNet.py:131-135): res_conv and the store are left out.
  * ap_resblock_fwd / _gate / _save return -22 in this mode (their h tensors are fp32; ap_resblock_bwd_bf16 recomputes from an fp32
  * layer input this mode never forms: use ap_resblock_fwd_u_save + ap_resblock_bwd_bf16_saved).
- * ap_eps_fwd / ap_purify_* run the whole sweep. */
+ * ap_eps_fwd / ap_purify_* run the whole sweep.  ap_init_conv_u, ap_resblock_fwd_u and ap_resblock_fwd_u_save return -22 in every other
+ * mode and width.  ap_resblock_fwd_u launches of at most one 128-sample tile per CU run on 64-sample tiles (ap_resblock_bf16us.hip)
+ * with bit-identical results, as ap_resblock_fwd_gate's do. */
 int ap_init_conv_u(ap_ctx *ctx, const float *x, const float *part_t_layer0, void *u_out, int B, int L, void *stream);
 int ap_resblock_fwd_u(ap_ctx *ctx, int layer, const void *u_in, const float *part_t_next, void *u_out, void *g_image, int B, int L,
                       void *stream);
@@ -228,41 +234,50 @@ int ap_resblock_fwd_u_save(ap_ctx *ctx, int layer, const void *u_in, const float
  * block tolerance, but only 3-4 % faster (both forms sit at the board's power cap; the second launch's traffic and the doubled
  * staging eat the saved matrix energy) and, like the fp32 F(2,3) form, up to 3 x the direct fp32 kernel's error on a 2^40 dynamic
  * range (the direct split form stays within 2 x): opt-in, not the default.
- * ap_ctx_get_f32_form returns the form the block launches of this context will use. */
+ * ap_ctx_get_f32_form returns the form the block launches of this context will use.  ap_ctx_set_f32_form: AP_PREC_F32 and
+ * AP_PREC_F32_SPLIT contexts (-22 in the bf16 modes); at a width without a minimal-filtering kernel (res != 256) form 1 is accepted
+ * and ap_ctx_get_f32_form reports 0, the form that runs. */
 int ap_ctx_set_f32_form(ap_ctx *ctx, int form);
 int ap_ctx_get_f32_form(ap_ctx *ctx);
 
 /* ap_resblock_fwd_save: ap_resblock_fwd that also writes the pre-gate activations y = DilConv(u) + b (WaveNet.py:87) to
  * pre_gate [B][2C][L] (rows 0..C-1 the tanh half, C..2C-1 the sigmoid half): what the backward of :90 needs, kept by the
  * differentiable purifier (the reference's autograd keeps it too) so that the adjoint does not recompute the dilated conv.
- * AP_PREC_F32 contexts only (-22 otherwise). */
+ * AP_PREC_F32 contexts only, res_channels 64 or 256 (-22 otherwise). */
 int ap_resblock_fwd_save(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out, float *skip,
                          float *pre_gate, int accumulate_skip, int B, int L, void *stream);
 
 /* ap_final_affine: final_conv (WaveNet.py:160-162,170) on skip*sqrt(1/N) (WaveNet.py:135) fused
  * with an affine update of the clip:  eps = W_f2 ReLU(W_f1 (skip*sqrt(1/N)) + b_f1) + b_f2;
  *   out = ca * x + cb * eps + cs * z.
- * eps_out and/or out may be NULL.  z: see header comment (NULL + cs != 0 -> Philox draw `draw`). */
+ * eps_out and/or out may be NULL.  z: see header comment (NULL + cs != 0 -> Philox draw `draw`).  Every precision mode and width;
+ * the bf16 modes run the S x S 1x1 on bf16 operands (fp32 accumulate), as their blocks do. */
 /* ap_resblock_bwd: input gradient of one Residual_block.forward (WaveNet.py:75-97; the reference's autograd does this for
  * robustness_eval/white_box_attack.py:392,437-439), two fused launches (ap_resblock_bwd.hip):
  *   dy = gate'(pre_gate) . ([W_res sqrt(1/2); W_skip]^T [dh_out; dskip])       -> dy_scratch [B][2C][L]
  *   dh_in = sqrt(1/2) dh_out + DilConv^T(dy)                                    (F(2,3) form of the transposed dilated conv)
  * dh_out = d loss / d h' [B][C][L] (zeros for the net's last layer, whose h' is unused), dskip = d loss / d skip_n [B][S][L] (the
  * same tensor for every layer: skip is their sum), pre_gate: what ap_resblock_fwd_save kept for this layer.  Parameters are
- * frozen (no weight gradients).  AP_PREC_F32, res = skip = 256 channels; ap_resblock_bwd_available says whether a shape is served. */
+ * frozen (no weight gradients).  AP_PREC_F32, res = skip = 256 channels; ap_resblock_bwd_available returns 1 exactly where
+ * ap_resblock_bwd serves (B, L) in this context. */
 int ap_resblock_bwd(ap_ctx *ctx, int layer, const float *dh_out, const float *dskip, const float *pre_gate, float *dy_scratch,
                     float *dh_in, int B, int L, void *stream);
 /* The backward kernels read their own weight images (fp32: 94 MB, bf16: 47 MB at the shipped shape).  ap_ctx_prepare_backward
  * allocates and packs them for the context's precision and synchronises the host -- like ap_ctx_load_wavenet it is NOT a launch
  * function (call it outside stream capture, once after every ap_ctx_load_wavenet; a second call is a no-op).  ap_resblock_bwd /
- * ap_resblock_bwd_bf16 return -22 until it has been called: they allocate nothing and stay hipGraph-capturable. */
+ * ap_resblock_bwd_bf16 return -22 until it has been called: they allocate nothing and stay hipGraph-capturable.
+ * ap_ctx_prepare_backward serves AP_PREC_F32, AP_PREC_BF16 and AP_PREC_BF16_STORE at res = skip = 256 channels; -22 for
+ * AP_PREC_F32_SPLIT and other widths. */
 int ap_ctx_prepare_backward(ap_ctx *ctx, void *stream);
 int ap_resblock_bwd_available(ap_ctx *ctx, int B, int L);
 /* The same gradient in AP_PREC_BF16 (bf16 MFMA operands, fp32 accumulate), from the layer INPUT instead of kept pre-gate activations --
  * on the bf16 matrix pipe the dilated conv is cheaper to recompute than a [B][2C][L] fp32 store per layer is to write:
  *   y = DilConv(bf16(h_in + part_t)) + b;  dy = gate'(y) . ([W_res sqrt(1/2); W_skip]^T [dh_out; dskip])  -> dy_scratch: a bf16 image
  *   [B][L][2C] (B L 1024 bytes);   dh_in = sqrt(1/2) dh_out + DilConv^T(dy).
- * AP_PREC_BF16 contexts, res = skip = 256 channels. */
+ * AP_PREC_BF16 contexts only, res = skip = 256 channels.  AP_PREC_BF16_STORE returns -22 (that mode packs the forward's GEMM1 image
+ * in the u image's permuted channel order, which this kernel does not stage): use ap_resblock_fwd_u_save + ap_resblock_bwd_bf16_saved.
+ * ap_resblock_bwd_bf16_available returns 1 where a bf16 backward serves (B, L) in this context: ap_resblock_bwd_bf16_saved, in both
+ * bf16 modes -- in AP_PREC_BF16 also ap_resblock_bwd_bf16. */
 int ap_resblock_bwd_bf16(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, const float *dh_out, const float *dskip,
                          void *dy_scratch, float *dh_in, int B, int L, void *stream);
 int ap_resblock_bwd_bf16_available(ap_ctx *ctx, int B, int L);
@@ -272,7 +287,8 @@ int ap_resblock_bwd_bf16_available(ap_ctx *ctx, int B, int L);
  * accumulator order) -- and ap_resblock_bwd_bf16_saved is ap_resblock_bwd_bf16 that reads them instead of h_in / part_t:
  *   dy = factors . ([W_res sqrt(1/2); W_skip]^T [dh_out; dskip]);   dh_in = sqrt(1/2) dh_out + DilConv^T(dy).
  * (|factor| <= 1 at 11 significant bits; dy is rounded to bf16 behind it either way.)  The reference's autograd keeps its
- * activations too (white_box_attack.py:392,437-439). */
+ * activations too (white_box_attack.py:392,437-439).  ap_resblock_fwd_gate_save: AP_PREC_BF16 only (AP_PREC_BF16_STORE keeps its factors
+ * with ap_resblock_fwd_u_save).  ap_resblock_bwd_bf16_saved: AP_PREC_BF16 and AP_PREC_BF16_STORE, res = skip = 256 channels. */
 size_t ap_gate_factor_bytes(int B, int L);
 int ap_resblock_fwd_gate_save(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out, void *g_image,
                               void *gate_factors, int B, int L, void *stream);

@@ -87,8 +87,9 @@ def _swish(x):
 # epsilon network   (WaveNet.py:53-172)
 # --------------------------------------------------------------------------
 def _bf16(t: torch.Tensor) -> torch.Tensor:
-    """Round-to-nearest-even to bfloat16 and back: what the AP_PREC_BF16 kernels feed the matrix cores."""
-    return t.to(torch.bfloat16).float()
+    """Round-to-nearest-even to bfloat16 and back: what the AP_PREC_BF16 kernels feed the matrix cores.  (Back to the input's
+    own dtype: the rounded values are exact in fp32 and fp64 alike, so the block can be evaluated in either.)"""
+    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def winograd_dilated_conv(u: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, d: int) -> torch.Tensor:

@@ -605,7 +605,7 @@ def test_backward_launches_refuse_to_run_before_the_images_are_built(dev):
     ap_ctx_prepare_backward -- and again after the weights are re-loaded -- they return -22 and say what to call."""
     from audiopure_amd import _native as N
     cfg = synth.mini_wavenet_config(256, 12, 12)
-    for mode, fn in (("f32", "ap_resblock_bwd"), ("bf16", "ap_resblock_bwd_bf16")):
+    for mode, fn in (("f32", "ap_resblock_bwd"), ("bf16", "ap_resblock_bwd_bf16"), ("bf16s", "ap_resblock_bwd_bf16_saved")):
         net, _ = _net(cfg, dev, seed=3)
         net.set_precision(mode)
         eng = net.engine()
@@ -615,15 +615,21 @@ def test_backward_launches_refuse_to_run_before_the_images_are_built(dev):
         h = torch.zeros((B, 256, L), device=dev)
         pt = torch.zeros(256, device=dev)
         o = torch.empty_like(h)
+        fac = torch.zeros(lib.ap_gate_factor_bytes(B, L), dtype=torch.uint8, device=dev)
 
         def call():
             if mode == "f32":
                 return lib.ap_resblock_bwd(eng.ctx, 0, N.ptr(h), N.ptr(h), N.ptr(t), N.ptr(t), N.ptr(o), B, L, N.stream())
+            if mode == "bf16s":
+                return lib.ap_resblock_bwd_bf16_saved(eng.ctx, 0, fac.data_ptr(), N.ptr(h), N.ptr(h), 0, t.data_ptr(), N.ptr(o), B, L, N.stream())
             return lib.ap_resblock_bwd_bf16(eng.ctx, 0, N.ptr(h), N.ptr(pt), N.ptr(h), N.ptr(h), t.data_ptr(), N.ptr(o), B, L, N.stream())
         assert call() == -22 and b"ap_ctx_prepare_backward" in lib.ap_last_error()
         N.check(lib.ap_ctx_prepare_backward(eng.ctx, N.stream()))
         N.check(lib.ap_ctx_prepare_backward(eng.ctx, N.stream()))      # a second call is a no-op
         assert call() == 0
+        if mode == "bf16s":                                            # the recomputing bf16 backward never serves this mode
+            rc = lib.ap_resblock_bwd_bf16(eng.ctx, 0, N.ptr(h), N.ptr(pt), N.ptr(h), N.ptr(h), t.data_ptr(), N.ptr(o), B, L, N.stream())
+            assert rc == -22 and b"ap_resblock_bwd_bf16_saved" in lib.ap_last_error()
         with torch.no_grad():
             net.init_conv[0].conv.bias.add_(1.0)                       # parameters changed: engine() re-loads, the images are stale
         eng2 = net.engine()
