@@ -435,45 +435,19 @@ int check_run(ap_ctx *ctx, int B, int L, void *ws, size_t ws_bytes, const char *
 // one AP_PREC_BF16_STORE block launch (its own pair of profile events: kind 0)
 int launch_resblock_u_timed(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st,
                             void *fout = nullptr) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->profile) {
-    if (ctx->ev_used + 2 > ctx->ev.size())
-      for (int i = 0; i < 2; i++) {
-        hipEvent_t e;
-        AP_HIP(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-      }
-    e0 = ctx->ev[ctx->ev_used];
-    e1 = ctx->ev[ctx->ev_used + 1];
-    if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
-    ctx->ev_kind[ctx->ev_used / 2] = 0;
-    ctx->ev_used += 2;
-    AP_HIP(hipEventRecord(e0, st));
-  }
+  ProfileSpan span;
+  if (int e = span.begin(ctx, 0, st)) return e;
   const int rc = launch_resblock_bf16u(ctx, layer, uin, pt_next, uout, gout, B, L, st, fout);
-  if (e1) AP_HIP(hipEventRecord(e1, st));
+  if (int e = span.end()) return e;
   return rc;
 }
 
 // one skip GEMM (its own pair of profile events: kind 1)
 int skip_gemm_timed(ap_ctx *ctx, int n0, int nl, const Ws &w, int B, int L, hipStream_t st) {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (ctx->profile) {
-    if (ctx->ev_used + 2 > ctx->ev.size())
-      for (int i = 0; i < 2; i++) {
-        hipEvent_t e;
-        AP_HIP(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-      }
-    e0 = ctx->ev[ctx->ev_used];
-    e1 = ctx->ev[ctx->ev_used + 1];
-    if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
-    ctx->ev_kind[ctx->ev_used / 2] = 1;
-    ctx->ev_used += 2;
-    AP_HIP(hipEventRecord(e0, st));
-  }
+  ProfileSpan span;
+  if (int e = span.begin(ctx, 1, st)) return e;
   const int rc = launch_skipgemm_bf16(ctx, n0, nl, w.gimg, w.skip, n0 > 0, B, L, st);
-  if (e1) AP_HIP(hipEventRecord(e1, st));
+  if (int e = span.end()) return e;
   return rc;
 }
 
@@ -576,36 +550,28 @@ extern "C" int ap_init_conv_u(ap_ctx *ctx, const float *x, const float *part_t_l
 
 extern "C" int ap_resblock_fwd_u(ap_ctx *ctx, int layer, const void *u_in, const float *part_t_next, void *u_out, void *g_image, int B, int L,
                                  void *stream) {
-  if (!ctx || !ctx->loaded || !u_in || !g_image) { set_error("ap_resblock_fwd_u: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd_u: layer=%d B=%d L=%d", layer, B, L); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd_u", ctx, u_in && g_image, layer, B, L, u_in, "u_in", u_out, "u_out")) return e;
   if (u_out && !part_t_next) { set_error("ap_resblock_fwd_u: u_out needs the next layer's part_t"); return -22; }
-  if (u_in == u_out) { set_error("ap_resblock_fwd_u: u_out must not alias u_in"); return -22; }
   return launch_resblock_u_timed(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream);
 }
 
 extern "C" int ap_resblock_fwd(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
                                float *skip, int accumulate_skip, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !h_in || !part_t_layer || !h_out || !skip) { set_error("ap_resblock_fwd: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (h_in == h_out) { set_error("ap_resblock_fwd: h_out must not alias h_in"); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd", ctx, h_in && part_t_layer && h_out && skip, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate_skip, B, L, (hipStream_t)stream);
 }
 
 extern "C" int ap_resblock_fwd_gate(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
                                     void *g_image, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !h_in || !part_t_layer || !g_image) { set_error("ap_resblock_fwd_gate: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd_gate: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (h_in == h_out) { set_error("ap_resblock_fwd_gate: h_out must not alias h_in"); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd_gate", ctx, h_in && part_t_layer && g_image, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   if (ctx->cfg.precision != AP_PREC_BF16) { set_error("ap_resblock_fwd_gate: AP_PREC_BF16 only"); return -22; }
   return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, nullptr, g_image);
 }
 
 extern "C" int ap_resblock_fwd_u_save(ap_ctx *ctx, int layer, const void *u_in, const float *part_t_next, void *u_out, void *g_image,
                                       void *gate_factors, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !u_in || !g_image || !gate_factors) { set_error("ap_resblock_fwd_u_save: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd_u_save: layer=%d B=%d L=%d", layer, B, L); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd_u_save", ctx, u_in && g_image && gate_factors, layer, B, L, u_in, "u_in", u_out, "u_out")) return e;
   if (u_out && !part_t_next) { set_error("ap_resblock_fwd_u_save: u_out needs the next layer's part_t"); return -22; }
-  if (u_in == u_out) { set_error("ap_resblock_fwd_u_save: u_out must not alias u_in"); return -22; }
   return launch_resblock_u_timed(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream, gate_factors);
 }
 
@@ -616,9 +582,7 @@ extern "C" size_t ap_gate_factor_bytes(int B, int L) {
 
 extern "C" int ap_resblock_fwd_gate_save(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
                                          void *g_image, void *gate_factors, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !h_in || !part_t_layer || !g_image || !gate_factors) { set_error("ap_resblock_fwd_gate_save: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd_gate_save: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (h_in == h_out) { set_error("ap_resblock_fwd_gate_save: h_out must not alias h_in"); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd_gate_save", ctx, h_in && part_t_layer && g_image && gate_factors, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   if (ctx->cfg.precision != AP_PREC_BF16) { set_error("ap_resblock_fwd_gate_save: AP_PREC_BF16 only"); return -22; }
   return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, nullptr, g_image, gate_factors);
 }
@@ -632,9 +596,7 @@ extern "C" int ap_skip_gemm(ap_ctx *ctx, int layer0, int n_layers, const void *g
 
 extern "C" int ap_resblock_fwd_save(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
                                     float *skip, float *pre_gate, int accumulate_skip, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !h_in || !part_t_layer || !h_out || !skip || !pre_gate) { set_error("ap_resblock_fwd_save: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("ap_resblock_fwd_save: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (h_in == h_out) { set_error("ap_resblock_fwd_save: h_out must not alias h_in"); return -22; }
+  if (int e = check_block_args("ap_resblock_fwd_save", ctx, h_in && part_t_layer && h_out && skip && pre_gate, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate_skip, B, L, (hipStream_t)stream, pre_gate);
 }
 

@@ -113,6 +113,46 @@ struct ap_ctx {
   int skip_group;               // AP_PREC_BF16: layers per skip GEMM of the deferred-skip form (0: fused block, skip per layer)
 };
 
+namespace ap {
+// One launch's (start, stop) event pair for ap_profile_read / ap_profile_read_split (bench.py's roofline leg).  Events are created
+// lazily and reused after a reset, one pair per launch; with ctx->profile off nothing is taken and nothing recorded.
+struct ProfileSpan {
+  hipEvent_t stop = nullptr;
+  hipStream_t st = nullptr;
+  int begin(ap_ctx *ctx, int kind, hipStream_t stream) {        // kind: ap_ctx::ev_kind
+    if (!ctx->profile) return 0;
+    if (ctx->ev_used + 2 > ctx->ev.size())
+      for (int i = 0; i < 2; i++) {
+        hipEvent_t e;
+        AP_HIP(hipEventCreate(&e));
+        ctx->ev.push_back(e);
+      }
+    const hipEvent_t start = ctx->ev[ctx->ev_used];
+    stop = ctx->ev[ctx->ev_used + 1];
+    st = stream;
+    if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
+    ctx->ev_kind[ctx->ev_used / 2] = (char)kind;
+    ctx->ev_used += 2;
+    AP_HIP(hipEventRecord(start, st));
+    return 0;
+  }
+  int end() {
+    if (stop) AP_HIP(hipEventRecord(stop, st));
+    return 0;
+  }
+};
+
+// What every block entry point of the C-ABI checks first (`who` is its name): the context is loaded and no required pointer is
+// null (`ptrs`), layer and shape are in range, the output does not alias the input.  0, or -22 with the error text set.
+inline int check_block_args(const char *who, const ap_ctx *ctx, bool ptrs, int layer, int B, int L, const void *in, const char *in_name,
+                            const void *out, const char *out_name) {
+  if (!ctx || !ctx->loaded || !ptrs) { set_error("%s: not loaded / null", who); return -22; }
+  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { set_error("%s: layer=%d B=%d L=%d", who, layer, B, L); return -22; }
+  if (in == out) { set_error("%s: %s must not alias %s", who, out_name, in_name); return -22; }
+  return 0;
+}
+}  // namespace ap
+
 struct ap_m5 {
   int n_output, n_channel, k1, stride;
   float *slab;
@@ -120,54 +160,11 @@ struct ap_m5 {
   float *fcw, *fcb;
 };
 
-// kernel launchers (defined in the .hip files)
 #ifdef __HIPCC__
-namespace ap {
-// row of accumulator register r of a 32x32 MFMA tile held by lane half hh
-__device__ __forceinline__ int rowoff(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-// exp(x) on the hardware exp2 with a compensated argument: ~2 ulp over the range the gate uses.
-__device__ __forceinline__ float exp_acc(float x) {
-  const float L2E_HI = 1.44269502162933349609375f;   // float(log2 e)
-  const float L2E_LO = 1.92596299e-8f;               // log2 e - L2E_HI
-  float t = x * L2E_HI;
-  float r = __builtin_fmaf(x, L2E_HI, -t);
-  r = __builtin_fmaf(x, L2E_LO, r);
-  float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * 0.693147182464599609375f, e);
-}
-
-// tanh(a) * sigmoid(b) = (E - 1) / ((E + 1) (1 + F)),  E = e^{2a}, F = e^{-b}   (WaveNet.py:90)
-__device__ __forceinline__ float gate(float a, float b) {
-  a = fminf(fmaxf(a, -15.0f), 15.0f);    // tanh(+-15) == +-1 in fp32
-  b = fmaxf(b, -80.0f);                  // keep F finite: sigmoid(-80) ~ 1.8e-35
-  float E = exp_acc(2.0f * a);
-  float F = exp_acc(-b);
-  return (E - 1.0f) * __builtin_amdgcn_rcpf((E + 1.0f) * (1.0f + F));
-}
-
-// Which (clip, tile) a workgroup of a one-tile-per-workgroup block kernel takes.  Placement only -- any bijection gives the same
-// results; this one is for the per-XCD L2s: workgroups b, b + 8, ... share an XCD (round-robin dispatch), so each XCD takes a
-// contiguous run of (clip, position) work, and inside a clip position p maps to tile r + k s (residue classes r = 0 .. s-1 in
-// turn, s = dilation / tile width capped at 16): the tiles an XCD holds at one time then include the ones d columns away,
-// whose centre columns are this tile's +-d taps.
-__device__ __forceinline__ void ap_tile_of_block(int bid, int nblk, int ntiles, int d, int tile_cols, int &b, int &tile) {
-  const int xcd = bid & 7, idx = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  b = logical / ntiles;
-  int p = logical % ntiles;
-  const int s = min(max(d / tile_cols, 1), 16);
-  if (s > 1) {
-    const int wq = ntiles / s, wrem = ntiles % s, cut = wrem * (wq + 1);
-    const int cls = p < cut ? p / (wq + 1) : wrem + (p - cut) / wq;
-    const int k = p < cut ? p % (wq + 1) : (p - cut) % wq;
-    p = cls + k * s;
-  }
-  tile = p;
-}
-}  // namespace ap
+#include "ap_device.h"   // what only kernels need
 #endif
 
+// kernel launchers (defined in the .hip files)
 namespace ap {
 int launch_fold_and_pack(ap_ctx *ctx, const float *blob, hipStream_t st);
 int launch_embed(ap_ctx *ctx, float step, float *part_t, hipStream_t st);

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256, 1) void conv2d_w3_kernel(ConvW3Args a) {
       __syncthreads();
     }
 
-    // ---- output transform, bias, residual, ReLU; lane (j, hh) of column tile ct holds pair column n0 + 32 ct + j, rows crowoff
+    // ---- output transform, bias, residual, ReLU; lane (j, hh) of column tile ct holds pair column n0 + 32 ct + j, rows rowoff
     const __amdgpu_buffer_rsrc_t ors = uni_rsrc(a.out, obytes);
     const __amdgpu_buffer_rsrc_t rrs = uni_rsrc(a.res ? a.res : a.out, a.res ? rbytes : 0u);
 #pragma unroll
@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void conv2d_w3_kernel(ConvW3Args a) {
           const __amdgpu_buffer_rsrc_t prs = uni_rsrc(a.part + (size_t)zs * a.B * a.Cout * HW, rbytes);
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            const int ro = (r & 3) + 8 * (r >> 2);
+            const int ro = rowoff(r, 0);
             const f32x2 o = {(acc[0][rt][ct][r] + acc[1][rt][ct][r]) + acc[2][rt][ct][r], (acc[1][rt][ct][r] - acc[2][rt][ct][r]) + acc[3][rt][ct][r]};
             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), prs, er, ro * HW * 4, 0);
           }
@@ -332,13 +332,13 @@ __global__ __launch_bounds__(256, 1) void conv2d_w3_kernel(ConvW3Args a) {
         float bv[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int ro = (r & 3) + 8 * (r >> 2);
+          const int ro = rowoff(r, 0);
           bv[r] = a.bias ? a.bias[co0 + ro] : 0.f;
           rv[r] = a.res ? __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rrs, er, ro * HW * 4, 0)) : f32x2{0.f, 0.f};
         }
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int ro = (r & 3) + 8 * (r >> 2);
+          const int ro = rowoff(r, 0);
           float y0 = (acc[0][rt][ct][r] + acc[1][rt][ct][r]) + acc[2][rt][ct][r];
           float y1 = (acc[1][rt][ct][r] - acc[2][rt][ct][r]) + acc[3][rt][ct][r];
           y0 = (y0 + bv[r]) + rv[r][0];                          // (bias, then residual: the order of the direct kernels)

@@ -25,8 +25,6 @@ struct ConvArgs {
   int o_coff;        // first channel of that slice (streamed-weight kernel and its split-K reduce only)
 };
 
-__device__ __forceinline__ int crowoff(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
 __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs a) {
   __shared__ float As[2][CBK][CBM];
   __shared__ float Bs[2][CBK][CBN];
@@ -91,13 +89,13 @@ __global__ __launch_bounds__(256) void conv2d_f32_kernel(ConvArgs a) {
     __syncthreads();
   }
 
-  // epilogue: lane (j, hh) holds column n0 + 32 wn + j, rows m0 + 32 wm + crowoff(r, hh)
+  // epilogue: lane (j, hh) holds column n0 + 32 wn + j, rows m0 + 32 wm + rowoff(r, hh)
   const int nn = n0 + 32 * wn + j;
   if (nn < N) {
     const int ob = nn / HoWo, op = nn % HoWo;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      const int m = m0 + 32 * wm + crowoff(r, hh);
+      const int m = m0 + 32 * wm + rowoff(r, hh);
       if (m < Mg) {
         const int co = g * Mg + m;
         const size_t off = ((size_t)ob * a.Cout + co) * HoWo + op;
@@ -283,7 +281,7 @@ __global__ __launch_bounds__(256) void conv2d_f32_big_kernel(ConvArgs a) {
       for (int x_ = 0; x_ < 2; x_++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int m = m0 + 64 * wm + 32 * x_ + crowoff(r, hh);
+          const int m = m0 + 64 * wm + 32 * x_ + rowoff(r, hh);
           if (m < Mg) {
             const int co = g * Mg + m;
             const size_t off = ((size_t)ob * a.Cout + co) * HoWo + op;
@@ -517,7 +515,7 @@ __global__ __launch_bounds__(256, 5) void conv2d_f32_big2_kernel(ConvArgs a, con
         if (early) fetch_operands();
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int r = 0; r < 16; r++) patch[crowoff(r, ehh) * 32 + ej] = acc[x_][y_][r];
+        for (int r = 0; r < 16; r++) patch[rowoff(r, ehh) * 32 + ej] = acc[x_][y_][r];
         asm volatile("" ::: "memory");
         if (!early) fetch_operands();
 #pragma unroll
@@ -551,7 +549,7 @@ __global__ __launch_bounds__(256, 5) void conv2d_f32_big2_kernel(ConvArgs a, con
       for (int x_ = 0; x_ < NX; x_++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int m = m0 + 32 * NX * wm + 32 * x_ + crowoff(r, hh);
+          const int m = m0 + 32 * NX * wm + 32 * x_ + rowoff(r, hh);
           if (m < Mg) {
             const int co = g * Mg + m;
             const size_t off = ((size_t)ob * a.Cout + co) * HoWo + op;
@@ -596,10 +594,6 @@ __global__ void conv_splitk_reduce_kernel(ConvArgs a, size_t total) {
 // 16-row chunk and wave instead of 32 of 64.  Weights come pre-split as A fragments ([group][row tile][k'/16][split]
 // [lane][8 bf16]); a thread stages 8 consecutive k' of one column (8 gathers HW apart -> 3 ds_write_b128 into the
 // [column][k'] bf16 images, 48-B rows: conflict-free b128 fragment reads).
-typedef __bf16 cbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cbf16x2 __attribute__((ext_vector_type(2)));
-typedef float cf32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int cu32x4 __attribute__((ext_vector_type(4)));
 
 typedef _Float16 ch16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 ch16x2 __attribute__((ext_vector_type(2)));
@@ -607,13 +601,6 @@ typedef _Float16 ch16x2 __attribute__((ext_vector_type(2)));
 // bits), three partial products on v_mfma_f32_32x32x16_f16, weights x 2^4 at pack time and activations x 2^4 at staging
 // (exact; the epilogue multiplies by 2^-8), scaled values clamped to +-60000.
 constexpr float CWSC = 16.0f, CXSC = 16.0f;
-
-__device__ __forceinline__ void csplit3(float x, __bf16 (&p)[3]) {
-  p[0] = (__bf16)x;
-  const float r1 = x - (float)p[0];
-  p[1] = (__bf16)r1;
-  p[2] = (__bf16)(r1 - (float)p[1]);
-}
 
 template <int BM, int BN, bool H16 = false>
 __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const void *__restrict__ afrag) {
@@ -636,11 +623,11 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
   const int HW = a.H * a.W;
   const float *xb = a.x + ((size_t)bb * a.x_cstride + a.x_coff + (size_t)g * Cg + 8 * ko) * HW;
   const int MT = (Mg + 31) / 32, KS = Kg / 16, CPT = Cg / BK;
-  const cu32x4 *af[NX];
+  const u32x4 *af[NX];
 #pragma unroll
   for (int x_ = 0; x_ < NX; x_++) {
     const int mt = min((m0 >> 5) + NX * wm + x_, MT - 1);
-    af[x_] = reinterpret_cast<const cu32x4 *>(afrag) + ((size_t)g * MT + mt) * KS * NS * 64 + lane;
+    af[x_] = reinterpret_cast<const u32x4 *>(afrag) + ((size_t)g * MT + mt) * KS * NS * 64 + lane;
   }
   const int nchunk = KK * CPT;
   float br[8];
@@ -656,28 +643,28 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
       br[i] = ok ? v : 0.f;
     }
   };
-  auto load_a = [&](cu32x4(&aa)[NX][NS], int c) {
+  auto load_a = [&](u32x4(&aa)[NX][NS], int c) {
 #pragma unroll
     for (int x_ = 0; x_ < NX; x_++)
 #pragma unroll
       for (int sp = 0; sp < NS; sp++) aa[x_][sp] = af[x_][(size_t)(NS * c + sp) * 64];
   };
   auto store_b = [&](int buf) {
-    cu32x4 pk[NS];
+    u32x4 pk[NS];
 #pragma unroll
     for (int pr = 0; pr < 4; pr++) {
       float v0 = br[2 * pr], v1 = br[2 * pr + 1];
       if constexpr (H16) {
-        const cf32x2 v = {__builtin_amdgcn_fmed3f(v0 * CXSC, -60000.0f, 60000.0f),
+        const f32x2 v = {__builtin_amdgcn_fmed3f(v0 * CXSC, -60000.0f, 60000.0f),
                           __builtin_amdgcn_fmed3f(v1 * CXSC, -60000.0f, 60000.0f)};
         const ch16x2 hi = __builtin_convertvector(v, ch16x2);
-        const ch16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, cf32x2), ch16x2);
+        const ch16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hi, f32x2), ch16x2);
         pk[0][pr] = __builtin_bit_cast(unsigned, hi);
         pk[1][pr] = __builtin_bit_cast(unsigned, lo);
       } else {
 #pragma unroll
         for (int sp = 0; sp < 3; sp++) {
-          const unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector(cf32x2{v0, v1}, cbf16x2));
+          const unsigned w = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
           pk[sp][pr] = w;
           if (sp < 2) {
             v0 -= __builtin_bit_cast(float, w << 16);
@@ -687,7 +674,7 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
       }
     }
 #pragma unroll
-    for (int sp = 0; sp < NS; sp++) *reinterpret_cast<cu32x4 *>(&Bs[buf][sp][nl * RS + ko * 16]) = pk[sp];
+    for (int sp = 0; sp < NS; sp++) *reinterpret_cast<u32x4 *>(&Bs[buf][sp][nl * RS + ko * 16]) = pk[sp];
   };
   f32x16 acc[NX][NY];
 #pragma unroll
@@ -696,13 +683,13 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
     for (int y_ = 0; y_ < NY; y_++)
 #pragma unroll
       for (int r = 0; r < 16; r++) acc[x_][y_][r] = 0.f;
-  auto compute = [&](const cu32x4(&aa)[NX][NS], int buf) {
+  auto compute = [&](const u32x4(&aa)[NX][NS], int buf) {
 #pragma unroll
     for (int y_ = 0; y_ < NY; y_++) {
-      cu32x4 bv[NS];
+      u32x4 bv[NS];
 #pragma unroll
       for (int sp = 0; sp < NS; sp++)
-        bv[sp] = *reinterpret_cast<const cu32x4 *>(&Bs[buf][sp][(32 * NY * wn + 32 * y_ + j) * RS + hh * 16]);
+        bv[sp] = *reinterpret_cast<const u32x4 *>(&Bs[buf][sp][(32 * NY * wn + 32 * y_ + j) * RS + hh * 16]);
 #pragma unroll
       for (int x_ = 0; x_ < NX; x_++) {
         if constexpr (H16) {
@@ -713,7 +700,7 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
 #undef AP_CT
         } else {
 #define AP_CT(i, jx)                                                                                                       \
-  acc[x_][y_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cbf16x8, aa[x_][i]), __builtin_bit_cast(cbf16x8, bv[jx]), \
+  acc[x_][y_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, aa[x_][i]), __builtin_bit_cast(bf16x8, bv[jx]), \
                                                         acc[x_][y_], 0, 0, 0);
           AP_CT(0, 0) AP_CT(0, 1) AP_CT(1, 0) AP_CT(0, 2) AP_CT(2, 0) AP_CT(1, 1)
 #undef AP_CT
@@ -721,7 +708,7 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
       }
     }
   };
-  cu32x4 a0[NX][NS], a1[NX][NS];
+  u32x4 a0[NX][NS], a1[NX][NS];
   load_a(a0, 0);
   load_b(0);
   store_b(0);
@@ -748,7 +735,7 @@ __global__ __launch_bounds__(256, 3) void conv2d_split_kernel(ConvArgs a, const 
       for (int x_ = 0; x_ < NX; x_++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int m = m0 + 32 * NX * wm + 32 * x_ + crowoff(r, hh);
+          const int m = m0 + 32 * NX * wm + 32 * x_ + rowoff(r, hh);
           if (m < Mg) {
             const int co = g * Mg + m;
             const size_t off = ((size_t)ob * a.Cout + co) * HoWo + op;
@@ -786,7 +773,7 @@ __global__ void conv_pack_split_kernel(const float *__restrict__ w, const float 
     if (scale) v *= scale[co];
   }
   __bf16 p[3];
-  csplit3(v, p);
+  split3(v, p);
   const size_t frag = (((size_t)g * MT + mt) * KS + q) * 3;
 #pragma unroll
   for (int sp = 0; sp < 3; sp++) out[((frag + sp) * 64 + lane) * 8 + jj] = p[sp];
@@ -1728,7 +1715,7 @@ __global__ __launch_bounds__(NT >= 8 ? 512 : 256) void attention_mfma_kernel(con
     for (int kt = 0; kt < NT; kt++)
 #pragma unroll
       for (int r = 0; r < 16; r++) {
-        const int key = 32 * kt + crowoff(r, hh);               // the key this lane half holds in register r
+        const int key = 32 * kt + rowoff(r, hh);               // the key this lane half holds in register r
 #pragma unroll
         for (int ct = 0; ct < 2; ct++)
           o[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(vt[key * VS + 32 * ct + j], sc[kt][r], o[ct], 0, 0, 0);
@@ -1739,7 +1726,7 @@ __global__ __launch_bounds__(NT >= 8 ? 512 : 256) void attention_mfma_kernel(con
 #pragma unroll
     for (int ct = 0; ct < 2; ct++)
 #pragma unroll
-      for (int r = 0; r < 16; r++) op[(size_t)(32 * ct + crowoff(r, hh)) * T] = o[ct][r] * inv;
+      for (int r = 0; r < 16; r++) op[(size_t)(32 * ct + rowoff(r, hh)) * T] = o[ct][r] * inv;
   }
 }
 

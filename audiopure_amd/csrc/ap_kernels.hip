@@ -487,7 +487,7 @@ __global__ __launch_bounds__(C / 64 * TTK, 2) void resblock_f32_kernel(
 #pragma unroll
         for (int r = 0; r < 16; r++)
           hres[rt][ct][r] = __builtin_bit_cast(
-              float, __builtin_amdgcn_raw_buffer_load_b32(hrs, evoff[rt][ct], ((r & 3) + 8 * (r >> 2)) * L * 4, 2));   // nt: hits or passes without allocating
+              float, __builtin_amdgcn_raw_buffer_load_b32(hrs, evoff[rt][ct], rowoff(r, 0) * L * 4, 2));   // nt: hits or passes without allocating
   }
 
   {
@@ -523,14 +523,14 @@ __global__ __launch_bounds__(C / 64 * TTK, 2) void resblock_f32_kernel(
           for (int r = 0; r < 16; r++)
             // nt (also the skip store below): once-written streams must not displace the h rows in the XCD's L2, which
             // neighbouring tiles' taps and the residual read again
-            __builtin_nontemporal_store((hres[rt][ct][r] + acc[rt][ct][r]) * RS, &ho[rbase + (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)L]);
+            __builtin_nontemporal_store((hres[rt][ct][r] + acc[rt][ct][r]) * RS, &ho[rbase + (unsigned)rowoff(r, 0) * (unsigned)L]);
         } else if (accumulate) {
 #pragma unroll
           for (int r = 0; r < 16; r++)
-            unsafeAtomicAdd(&sk[rbase + (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)L], acc[rt][ct][r]);
+            unsafeAtomicAdd(&sk[rbase + (unsigned)rowoff(r, 0) * (unsigned)L], acc[rt][ct][r]);
         } else {
 #pragma unroll
-          for (int r = 0; r < 16; r++) __builtin_nontemporal_store(acc[rt][ct][r], &sk[rbase + (unsigned)((r & 3) + 8 * (r >> 2)) * (unsigned)L]);
+          for (int r = 0; r < 16; r++) __builtin_nontemporal_store(acc[rt][ct][r], &sk[rbase + (unsigned)rowoff(r, 0) * (unsigned)L]);
         }
       }
     }
@@ -561,49 +561,23 @@ int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, f
     return -22;
   }
   if (ctx->cfg.precision != AP_PREC_F32 && !g_force_f32) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (ctx->profile) {
-      if (ctx->ev_used + 2 > ctx->ev.size())
-        for (int i = 0; i < 2; i++) {
-          hipEvent_t e;
-          AP_HIP(hipEventCreate(&e));
-          ctx->ev.push_back(e);
-        }
-      e0 = ctx->ev[ctx->ev_used];
-      e1 = ctx->ev[ctx->ev_used + 1];
-      if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
-      ctx->ev_kind[ctx->ev_used / 2] = 0;
-      ctx->ev_used += 2;
-      AP_HIP(hipEventRecord(e0, st));
-    }
+    ProfileSpan span;
+    if (int e = span.begin(ctx, 0, st)) return e;
     int rc = ctx->cfg.precision == AP_PREC_BF16
                  ? (gout && !ub && !fout && g_no_bf16s != 1 && (g_no_bf16s == 2 || resblock_bf16s_serves(ctx, B, L))
                         ? launch_resblock_bf16s(ctx, layer, hin, pt, hout, gout, B, L, st)     // small batches: half-size tiles, bit-identical
                         : launch_resblock_bf16(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, ub, gout, fout))
                  : launch_resblock_split(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
-    if (e1) AP_HIP(hipEventRecord(e1, st));
+    if (int e = span.end()) return e;
     return rc;
   }
   const int C = ctx->C, S = ctx->S;
   const int d = 1 << (layer % ctx->cfg.dilation_cycle);
   if (!g_force_direct && resblock_f32w_serves(ctx, B, L)) {     // F(2,3) form of the dilated conv (ap_resblock_f32w.hip)
-    hipEvent_t w0 = nullptr, w1e = nullptr;
-    if (ctx->profile) {
-      if (ctx->ev_used + 2 > ctx->ev.size())
-        for (int i = 0; i < 2; i++) {
-          hipEvent_t e;
-          AP_HIP(hipEventCreate(&e));
-          ctx->ev.push_back(e);
-        }
-      w0 = ctx->ev[ctx->ev_used];
-      w1e = ctx->ev[ctx->ev_used + 1];
-      if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
-      ctx->ev_kind[ctx->ev_used / 2] = 0;
-      ctx->ev_used += 2;
-      AP_HIP(hipEventRecord(w0, st));
-    }
+    ProfileSpan span;
+    if (int e = span.begin(ctx, 0, st)) return e;
     const int rcw = launch_resblock_f32w(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, aout);
-    if (w1e) AP_HIP(hipEventRecord(w1e, st));
+    if (int e = span.end()) return e;
     return rcw;
   }
   if (!hout) {
@@ -614,22 +588,8 @@ int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, f
   const float *w2p = ctx->w2p + (size_t)layer * (C + S) * C;
   const float *b1 = ctx->b1 + (size_t)layer * 2 * C;
   const float *b2 = ctx->b2 + (size_t)layer * (C + S);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (ctx->profile) {
-    if (ctx->ev_used + 2 > ctx->ev.size()) {
-      for (int i = 0; i < 2; i++) {
-        hipEvent_t e;
-        AP_HIP(hipEventCreate(&e));
-        ctx->ev.push_back(e);
-      }
-    }
-    ev0 = ctx->ev[ctx->ev_used];
-    ev1 = ctx->ev[ctx->ev_used + 1];
-    if (ctx->ev_kind.size() < ctx->ev.size() / 2) ctx->ev_kind.resize(ctx->ev.size() / 2, 0);
-    ctx->ev_kind[ctx->ev_used / 2] = 0;
-    ctx->ev_used += 2;
-    AP_HIP(hipEventRecord(ev0, st));
-  }
+  ProfileSpan span;
+  if (int e = span.begin(ctx, 0, st)) return e;
 #define AP_RB(CC, TK)                                                                                              \
   resblock_f32_kernel<CC, TK><<<(unsigned)B * ((L + TK - 1) / TK), CC / 64 * TK, 0, st>>>(                         \
       hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, (L + TK - 1) / TK, nullptr AP_ABLATE_ARG(g_ablate))
@@ -658,7 +618,7 @@ int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, f
   }
 #undef AP_RB
 #undef AP_RB_SAVE
-  if (ev1) AP_HIP(hipEventRecord(ev1, st));
+  if (int e = span.end()) return e;
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -32,66 +32,9 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int PT_ = 128;                 // time tile
 constexpr int KC_ = 32;                  // channels per staged chunk -> 96 K rows = 6 k-steps of 16
-constexpr int XS_ = 3 * KC_ + 8;         // bf16 per column row of the X image (208 B)
-constexpr int GS_ = 256 + 8;             // bf16 per column row of the g image (528 B)
 constexpr int PS_ = 32;                  // fp32 per row of the wave-private output patch (128 B)
-
-
-// tanh(a) sigmoid(b) = (1 - E) / ((1 + E)(1 + F)), E = e^(-2a), F = e^(-b).  a is clamped to [-16, 16] first (one v_med3;
-// tanh(+-16) rounds to +-1 in fp32, so the clamp changes no result): E stays finite, the sign comes out of 1 - E, and no
-// abs / copysign pair is needed.  F may overflow to +inf: the denominator is +inf then and the gate 0, which is the limit.
-// The same arithmetic, element for element, as gate_fast of tools/csrc/ap_resblock_bf16.hip (the two kernels are bit-identical).
-// On a pair of values: plain arithmetic as two-wide fp32 operations (v_pk_mul_f32 / v_pk_add_f32: one issue slot for two
-// gates; the file is built with -fno-slp-vectorize, so the pairing is written out), the three transcendentals per gate
-// stay scalar; the caller converts the pair to bf16 with one v_cvt_pk_bf16_f32.
-__device__ __forceinline__ f32x2 gate_fast2(f32x2 a, f32x2 b) {
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 den = (E + 1.0f) * (F + 1.0f);
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  return (1.0f - E) * r;
-}
-
-// gate_fast2 that also hands out the gate's two derivative factors (the white-box backward's operands: ap_resblock_bwd_bf16.hip):
-// f1 = d(tanh . sigmoid)/d(tanh arg) = sg (1 - th^2), f2 = d/d(sigmoid arg) = th sg (1 - sg), from the quantities the gate forms anyway
-// (sg = (1 + E) r, th = g (1 + F), th sg = g).  The returned gate is gate_fast2's, operation for operation: a forward pass that keeps
-// the factors writes the same h' and g image as one that does not.  F = +inf (sigmoid argument below -88): g = sg = 0 and 0 . inf is
-// taken as 0.
-__device__ __forceinline__ f32x2 gate_fast2_save(f32x2 a, f32x2 b, f32x2 &f1, f32x2 &f2) {
-#pragma clang fp contract(off)                                  // one operation order in every instantiation (1 - th th as an fma in some, not in others: seen)
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 opE = E + 1.0f, opF = F + 1.0f;
-  const f32x2 den = opE * opF;
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  const f32x2 g = (1.0f - E) * r;
-  const f32x2 sg = opE * r;
-  f32x2 th = g * opF;
-  th[0] = F[0] > 3.0e38f ? 0.f : th[0];
-  th[1] = F[1] > 3.0e38f ? 0.f : th[1];
-  f1 = sg * (1.0f - th * th);
-  f2 = g * (1.0f - sg);
-  return g;
-}
-
-using I0 = std::integral_constant<int, 0>;
-using I1 = std::integral_constant<int, 1>;
-using I2 = std::integral_constant<int, 2>;
-using I3 = std::integral_constant<int, 3>;
 
 }  // namespace
 
@@ -290,11 +233,11 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   // of ds_read_b128 are conflict-free iff the row stride is 14 (or 2) slots of 16 B mod 16 (208 B = 13 slots is 2-way); the
   // pack's ds_write_b128 is 2-way there (16 LDS cycles against the 13 its register transfer takes: measured free in round 2).
   // The window variants keep 208-byte rows (their scratch column quad leaves no LDS for longer ones).
-  constexpr int XS = (M16 && !WIN) ? 112 : XS_;
+  constexpr int XS = (M16 && !WIN) ? 112 : BF_XS;
   constexpr int SWZ = ((M16 && !WIN) || UB) ? 0 : 1;            // (UB: column pairs four apart per ds_write_b128 group -- conflict-free unswizzled)
   constexpr int XBYTES = (PT_ + (WIN ? 4 : 0)) * XS * 2;        // 26,624 B per X buffer (WIN: + a scratch column quad), two buffers
   constexpr int GOFF = 2 * XBYTES;
-  constexpr int POFF = GOFF + PT_ * GS_ * 2;                   // output patches: 8 waves x 32 x 32 fp32
+  constexpr int POFF = GOFF + PT_ * BF_GS * 2;                   // output patches: 8 waves x 32 x 32 fp32
   constexpr int PTOFF = POFF + NW * 32 * PS_ * 4;              // part_t (C floats)
   constexpr int BOFF = PTOFF + C * 4;                          // b1 (2C floats: filter | gate rows), b2 (2C: res | skip rows)
   constexpr int PNOFF = BOFF + 4 * C * 4;                      // UB: the next layer's part_t (C floats)
@@ -587,7 +530,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   const int rd16o = (c16 * XS) * 2 + ((q4 ^ (SWZ * 2 * (par16 ^ 1))) * 16);     // odd ct16
   const int rdoff = (j * XS + 8 * hh) * 2;                      // this lane's B-fragment byte offset inside an X buffer
   const int rdsw = SWZ * (__builtin_popcount((j >> 2) & 7) & 1) * 32;
-  const unsigned char *gb = lds + GOFF + (j * GS_ + 8 * hh) * 2;
+  const unsigned char *gb = lds + GOFF + (j * BF_GS + 8 * hh) * 2;
   float *patch = reinterpret_cast<float *>(lds + POFF) + wave * 32 * PS_;
   const float RS = 0.707106781186547524f;
 
@@ -951,7 +894,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
               const f32x2 g2 = (DBG & 32) ? a2 + b2 : gate_fast2(a2, b2);
               pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
             }
-            *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + 16 * h2 + c16) * GS_ + 32 * wave + 16 * rtp + 4 * q4) * 2) = make_uint2(pk[0], pk[1]);
+            *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + 16 * h2 + c16) * BF_GS + 32 * wave + 16 * rtp + 4 * q4) * 2) = make_uint2(pk[0], pk[1]);
           }
         __builtin_amdgcn_sched_barrier(0);
         return;
@@ -977,7 +920,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
           }
           pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
         }
-        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * GS_ + 32 * wave + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
+        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * BF_GS + 32 * wave + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
         if constexpr (SAVEF) {
           const uint64_t fb = (uint64_t)fout + (uint64_t)b_cur * ((uint64_t)ntiles * 131072u);
           const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)fb), fhi = __builtin_amdgcn_readfirstlane((uint32_t)(fb >> 32));
@@ -1030,7 +973,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       bf16x8 ba[4], bb[4];
       auto rdg = [&](bf16x8(&bq)[4], int ks) {
 #pragma unroll
-        for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (GS_ * 2) + (ks & (NKS - 1)) * 32);
+        for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (BF_GS * 2) + (ks & (NKS - 1)) * 32);
       };
       auto step = [&](const bf16x8 &a, const bf16x8(&use)[4], bf16x8(&nxt)[4], int ks) {
         rdg(nxt, ks + 1);
@@ -1173,10 +1116,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
         const __amdgpu_buffer_rsrc_t grs =
             __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)ghi << 32) | glo), 0, (int)((unsigned)L * 512u), 0x00020000);
         const int colw = 2 * wave + (ln >> 5), q = ln & 31;
-        const unsigned char *src = lds + GOFF + colw * (GS_ * 2) + q * 16;
+        const unsigned char *src = lds + GOFF + colw * (BF_GS * 2) + q * 16;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-          const u32x4 v = *reinterpret_cast<const u32x4 *>(src + 16 * i * (GS_ * 2));
+          const u32x4 v = *reinterpret_cast<const u32x4 *>(src + 16 * i * (BF_GS * 2));
           const int t = t0 + colw + 16 * i;
           const unsigned off = t < L ? (unsigned)t * 512u + (unsigned)q * 16u : 0x80000000u;   // outside the clip: dropped
           if constexpr (DBG & 256) asm volatile("" ::"v"(v));

@@ -19,28 +19,7 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4s __attribute__((ext_vector_type(4)));
-
 constexpr int SC_ = 256;                  // res = skip channels
-constexpr int SXS_ = 96 + 8;              // bf16 per column row of the X chunk image (3 taps x 32 channels; 208-byte rows)
-constexpr int SGS_ = 256 + 8;             // bf16 per column row of the g image (528-byte rows)
-constexpr unsigned SFR_ = 64 * 16;        // bytes of one row tile's fragment of a k-step
-
-// tanh(a) sigmoid(b): the arithmetic of ap_resblock_bf16p.hip's gate_fast2, operation for operation (the results must be its results)
-__device__ __forceinline__ f32x2 gate_pair(f32x2 a, f32x2 b) {
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 den = (E + 1.0f) * (F + 1.0f);
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  return (1.0f - E) * r;
-}
 
 }  // namespace
 
@@ -61,8 +40,8 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
                                                                 int ntiles) {
   constexpr int C = SC_;
   constexpr int NT = 64;
-  constexpr int XB = NT * SXS_;
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * XB + NT * SGS_];   // 26.6 KB X ring + 33.8 KB g image
+  constexpr int XB = NT * BF_XS;
+  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * XB + NT * BF_GS];   // 26.6 KB X ring + 33.8 KB g image
   __bf16 *gim = lds + 2 * XB;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -77,8 +56,8 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
   };
   const unsigned clip_bytes = (unsigned)C * (unsigned)L * 4u;
   const __amdgpu_buffer_rsrc_t hrs = uni_rsrc(hin + (size_t)b * C * L, clip_bytes);
-  const __amdgpu_buffer_rsrc_t w1rs = uni_rsrc(reinterpret_cast<const char *>(w1) + (size_t)wave * (8 * 6 * 2 * SFR_), 8 * 6 * 2 * SFR_);
-  const __amdgpu_buffer_rsrc_t w2rs = uni_rsrc(reinterpret_cast<const char *>(w2) + (size_t)wave * (2 * 16 * SFR_), 16 * SFR_);   // row tile 0 only
+  const __amdgpu_buffer_rsrc_t w1rs = uni_rsrc(reinterpret_cast<const char *>(w1) + (size_t)wave * (8 * 6 * 2 * BF_FR), 8 * 6 * 2 * BF_FR);
+  const __amdgpu_buffer_rsrc_t w2rs = uni_rsrc(reinterpret_cast<const char *>(w2) + (size_t)wave * (2 * 16 * BF_FR), 16 * BF_FR);   // row tile 0 only
   const __amdgpu_buffer_rsrc_t ptrs = uni_rsrc(pt, C * 4u);
   const unsigned lane16 = (unsigned)lane * 16u;
 
@@ -105,7 +84,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
     for (int tap = 0; tap < 3; tap++) {
       const bool ok = xv[tap] != 0x80000000u;
       const f32x4 u = {ok ? xr[tap][0] + pq[0] : 0.f, ok ? xr[tap][1] + pq[1] : 0.f, ok ? xr[tap][2] + pq[2] : 0.f, ok ? xr[tap][3] + pq[3] : 0.f};
-      *reinterpret_cast<bf16x4 *>(dst + sj * SXS_ + 32 * tap + 4 * sq) = __builtin_convertvector(u, bf16x4);
+      *reinterpret_cast<bf16x4 *>(dst + sj * BF_XS + 32 * tap + 4 * sq) = __builtin_convertvector(u, bf16x4);
     }
   };
 
@@ -123,7 +102,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
   auto load_a1 = [&](bf16x8(&a)[2], int step) {
 #pragma unroll
     for (int rt = 0; rt < 2; rt++)
-      a[rt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w1rs, lane16 + rt * SFR_, step * 2 * SFR_, 0));
+      a[rt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w1rs, lane16 + rt * BF_FR, step * 2 * BF_FR, 0));
   };
   bf16x8 a1[3][2];                                               // ring of three k-steps, requested two ahead (six per chunk: slot = ks % 3)
   load_a1(a1[0], 0);
@@ -133,7 +112,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
   __syncthreads();
 #pragma unroll 1
   for (int ch = 0; ch < 8; ch++) {
-    const __bf16 *xb = lds + (ch & 1) * XB + j * SXS_ + 8 * hh;
+    const __bf16 *xb = lds + (ch & 1) * XB + j * BF_XS + 8 * hh;
     if (ch + 1 < 8) issue_x(ch + 1);
 #pragma unroll
     for (int ks = 0; ks < 6; ks++) {
@@ -141,7 +120,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
       load_a1(a1[(ks + 2) % 3], nx < 48 ? nx : 47);
       bf16x8 bq[2];
 #pragma unroll
-      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(xb + 32 * ct * SXS_ + 16 * ks);
+      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(xb + 32 * ct * BF_XS + 16 * ks);
 #pragma unroll
       for (int rt = 0; rt < 2; rt++)
 #pragma unroll
@@ -159,7 +138,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
   unsigned eo[2];
   if constexpr (!NOH) {
 #pragma unroll
-    for (int i = 0; i < 3; i++) a2[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, i * SFR_, 0));
+    for (int i = 0; i < 3; i++) a2[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, i * BF_FR, 0));
   }
 
   // ---- gate -> g image [column][channel] (bf16); rows rowoff(4 qq .. 4 qq + 3, hh) are channels 32 wave + 8 qq + 4 hh ..
@@ -172,10 +151,10 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
       for (int e = 0; e < 4; e += 2) {
         const f32x2 a2v = {acc[0][ct][4 * qq + e], acc[0][ct][4 * qq + e + 1]};
         const f32x2 b2v = {acc[1][ct][4 * qq + e], acc[1][ct][4 * qq + e + 1]};
-        const f32x2 g2 = gate_pair(a2v, b2v);
+        const f32x2 g2 = gate_fast2(a2v, b2v);
         pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
       }
-      *reinterpret_cast<uint2 *>(gim + (32 * ct + j) * SGS_ + 32 * wave + 8 * qq + 4 * hh) = make_uint2(pk[0], pk[1]);
+      *reinterpret_cast<uint2 *>(gim + (32 * ct + j) * BF_GS + 32 * wave + 8 * qq + 4 * hh) = make_uint2(pk[0], pk[1]);
     }
   __syncthreads();
 
@@ -187,7 +166,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
     const unsigned off = t < L ? (unsigned)t * 512u + (unsigned)part * 64u : 0x80000000u;     // outside the clip: dropped
 #pragma unroll
     for (int i = 0; i < 4; i++)
-      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4s *>(gim + col * SGS_ + 32 * part + 8 * i), grs, off + 16u * i, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4 *>(gim + col * BF_GS + 32 * part + 8 * i), grs, off + 16u * i, 0, 0);
   }
   if constexpr (NOH) return;                                     // the net's last layer: its h' is never read (WaveNet.py:131-135)
   // the residual's h values in accumulator layout (the staging pass has just pulled these rows into L2), in flight under GEMM2
@@ -197,7 +176,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
     eo[ct] = t < L ? ((unsigned)(32 * wave + 4 * hh) * (unsigned)L + (unsigned)t) * 4u : 0x80000000u;
 #pragma unroll
     for (int r = 0; r < 16; r++)
-      hres[ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, eo[ct], ((r & 3) + 8 * (r >> 2)) * L * 4, 0));
+      hres[ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, eo[ct], rowoff(r, 0) * L * 4, 0));
   }
 
   // ---- GEMM2, res_conv rows: accumulators start from b2 + part_t (u = h + part_t re-enters the residual: alias semantics, WaveNet.py:77-84)
@@ -213,13 +192,13 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
       acr[1][4 * q + e] = v;
     }
   }
-  const __bf16 *gb = gim + j * SGS_ + 8 * hh;
+  const __bf16 *gb = gim + j * BF_GS + 8 * hh;
 #pragma unroll
   for (int ks = 0; ks < 16; ks++) {
-    if (ks + 3 < 16) a2[(ks + 3) & 3] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, (ks + 3) * SFR_, 0));
+    if (ks + 3 < 16) a2[(ks + 3) & 3] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, (ks + 3) * BF_FR, 0));
     bf16x8 bq[2];
 #pragma unroll
-    for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + 32 * ct * SGS_ + 16 * ks);
+    for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + 32 * ct * BF_GS + 16 * ks);
 #pragma unroll
     for (int ct = 0; ct < 2; ct++) acr[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks & 3], bq[ct], acr[ct], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
@@ -231,7 +210,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
 #pragma unroll
     for (int r = 0; r < 16; r++)
       __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (hres[ct][r] + acr[ct][r]) * RS), ors, eo[ct],
-                                            ((r & 3) + 8 * (r >> 2)) * L * 4, 0);
+                                            rowoff(r, 0) * L * 4, 0);
 }
 
 // at most one 128-sample tile per CU: the launches whose duration is one tile's latency on the persistent kernel

@@ -34,57 +34,8 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int PT_ = 128;                 // time tile
 constexpr int KC_ = 32;                  // channels per chunk -> 96 K rows = 6 k-steps of 16
-constexpr int XS_ = 3 * KC_ + 8;         // bf16 per column row of the X image (208 B: conflict-free ds_read_b128 B fragments)
-constexpr int GS_ = 256 + 8;             // bf16 per column row of the g image (528 B)
-
-// tanh(a) sigmoid(b) = (1 - E) / ((1 + E)(1 + F)), E = e^(-2a), F = e^(-b): the arithmetic of ap_resblock_bf16p.hip's gate_fast2,
-// operation for operation.
-__device__ __forceinline__ f32x2 gate_pair_u(f32x2 a, f32x2 b) {
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 den = (E + 1.0f) * (F + 1.0f);
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  return (1.0f - E) * r;
-}
-
-// the same gate, also handing out its two derivative factors sg (1 - th^2), th sg (1 - sg) (ap_resblock_bf16p.hip: gate_fast2_save; the
-// returned gate is gate_pair_u's, operation for operation)
-__device__ __forceinline__ f32x2 gate_pair_u_save(f32x2 a, f32x2 b, f32x2 &f1, f32x2 &f2) {
-#pragma clang fp contract(off)
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 opE = E + 1.0f, opF = F + 1.0f;
-  const f32x2 den = opE * opF;
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  const f32x2 g = (1.0f - E) * r;
-  const f32x2 sg = opE * r;
-  f32x2 th = g * opF;
-  th[0] = F[0] > 3.0e38f ? 0.f : th[0];
-  th[1] = F[1] > 3.0e38f ? 0.f : th[1];
-  f1 = sg * (1.0f - th * th);
-  f2 = g * (1.0f - sg);
-  return g;
-}
-
-using I0 = std::integral_constant<int, 0>;
-using I1 = std::integral_constant<int, 1>;
-using I2 = std::integral_constant<int, 2>;
-using I3 = std::integral_constant<int, 3>;
-
-__host__ __device__ __forceinline__ int swap23(int p) { return (p & ~12) | ((p & 4) << 1) | ((p & 8) >> 1); }
 
 }  // namespace
 
@@ -131,10 +82,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
     int L, int d, int ntiles, int nblk, void *__restrict__ gout,                              // this layer's g image [clip][L][256] bf16
     void *__restrict__ fout = nullptr) {                                                      // SAVEF: the gate's derivative factors
   constexpr int C = 256, NW = 8, NCH = C / KC_, NKS = C / 16;
-  constexpr int XS = XS_;
+  constexpr int XS = BF_XS;
   constexpr int XBYTES = PT_ * XS * 2;                         // 26,624 B per X buffer, two buffers
   constexpr int GOFF = 2 * XBYTES;
-  constexpr int BOFF = GOFF + PT_ * GS_ * 2;                   // b1 (2C floats: filter | gate rows), b2 res rows (C), next part_t (C)
+  constexpr int BOFF = GOFF + PT_ * BF_GS * 2;                   // b1 (2C floats: filter | gate rows), b2 res rows (C), next part_t (C)
   constexpr int LDS_BYTES = BOFF + 4 * C * 4;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
@@ -247,7 +198,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, w2_off + (wave * 2 * NKS + ks) * 1024, 0));
   };
   const int rdoff = (j * XS + 8 * hh) * 2;                      // this lane's B-fragment byte offset inside an X buffer
-  const unsigned char *gb = lds + GOFF + (j * GS_ + 8 * hh) * 2;
+  const unsigned char *gb = lds + GOFF + (j * BF_GS + 8 * hh) * 2;
   const float RS = 0.707106781186547524f;
 
   // ---- first tile: parameters and chunk-0 request
@@ -397,15 +348,15 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
           if constexpr (SAVEF) {
             typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
             f32x2 f1, f2;
-            g2 = gate_pair_u_save(a2, b2, f1, f2);
+            g2 = gate_fast2_save(a2, b2, f1, f2);
             fq[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{f1[0], f2[0]}, f16x2));       // (tanh factor, sigmoid factor) of element e
             fq[e + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{f1[1], f2[1]}, f16x2));
           } else {
-            g2 = gate_pair_u(a2, b2);
+            g2 = gate_fast2(a2, b2);
           }
           pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
         }
-        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * GS_ + 32 * wave + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
+        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * BF_GS + 32 * wave + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
         if constexpr (SAVEF) {
           const uint64_t fb = (uint64_t)fout + (uint64_t)b_cur * ((uint64_t)ntiles * 131072u);
           const uint32_t flo = __builtin_amdgcn_readfirstlane((uint32_t)fb), fhi = __builtin_amdgcn_readfirstlane((uint32_t)(fb >> 32));
@@ -452,7 +403,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
       bf16x8 ba[4], bb[4];
       auto rdg = [&](bf16x8(&bq)[4], int ks) {
 #pragma unroll
-        for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (GS_ * 2) + (ks & (NKS - 1)) * 32);
+        for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (BF_GS * 2) + (ks & (NKS - 1)) * 32);
       };
       auto step = [&](const bf16x8 &a, const bf16x8(&use)[4], bf16x8(&nxt)[4], int ks) {
         rdg(nxt, ks + 1);
@@ -533,10 +484,10 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
       const __amdgpu_buffer_rsrc_t grs =
           __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)ghi << 32) | glo), 0, (int)((unsigned)L * 512u), 0x00020000);
       const int colw = 2 * wave + (ln >> 5), q = ln & 31;
-      const unsigned char *src = lds + GOFF + colw * (GS_ * 2) + q * 16;
+      const unsigned char *src = lds + GOFF + colw * (BF_GS * 2) + q * 16;
 #pragma unroll
       for (int i = 0; i < 8; i++) {
-        const u32x4 v = *reinterpret_cast<const u32x4 *>(src + 16 * i * (GS_ * 2));
+        const u32x4 v = *reinterpret_cast<const u32x4 *>(src + 16 * i * (BF_GS * 2));
         const int t = t0 + colw + 16 * i;
         const unsigned off = t < L ? (unsigned)t * 512u + (unsigned)q * 16u : 0x80000000u;   // outside the clip: dropped
         __builtin_amdgcn_raw_buffer_store_b128(v, grs, off, 0, 2);

@@ -6,7 +6,7 @@
 //   * GEMM1: accumulators start from b1; the same bf16 operands (a chunk's (column, tap) operand is one 64-byte row of the image, channel
 //     positions in the image's own order; the weight image packed with the same K permutation) enter the same
 //     v_mfma_f32_32x32x16_bf16 sequence per output element, chunk by chunk, six k-steps each;
-//   * the gate: gate_pair_u's arithmetic on the same channel pairs, bf16 RNE;
+//   * the gate: gate_fast2's arithmetic on the same channel pairs, bf16 RNE;
 //   * GEMM2 (res_conv): accumulators start from b2, sixteen k-steps in order; u' = bf16((u + acc) sqrt(1/2) + part_t of the next layer)
 //     with the three operations rounded separately (fp contract off), as in the persistent kernel's epilogue.
 // tests: one- and two-clip chains against the 512-clip batch bit for bit (tests/test_gpu_bf16_store.py), kernel against kernel on random
@@ -19,27 +19,7 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-
 constexpr int UC_ = 256;                  // res = skip channels
-constexpr int UXS_ = 96 + 8;              // bf16 per column row of the X chunk image (3 taps x 32 channel positions; 208-byte rows)
-constexpr int UGS_ = 256 + 8;             // bf16 per column row of the g image (528-byte rows)
-constexpr unsigned UFR_ = 64 * 16;        // bytes of one row tile's fragment of a k-step
-
-// tanh(a) sigmoid(b): ap_resblock_bf16u.hip's gate_pair_u, operation for operation (the results must be its results)
-__device__ __forceinline__ f32x2 gate_pair_us(f32x2 a, f32x2 b) {
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 den = (E + 1.0f) * (F + 1.0f);
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  return (1.0f - E) * r;
-}
 
 }  // namespace
 
@@ -52,8 +32,8 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
                                                                  const float *__restrict__ b1, const float *__restrict__ b2, int L, int d, int ntiles) {
   constexpr int C = UC_;
   constexpr int NT = 64;
-  constexpr int XB = NT * UXS_;
-  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * XB + NT * UGS_];   // 26.6 KB X ring + 33.8 KB g image
+  constexpr int XB = NT * BF_XS;
+  __shared__ __attribute__((aligned(16))) __bf16 lds[2 * XB + NT * BF_GS];   // 26.6 KB X ring + 33.8 KB g image
   __bf16 *gim = lds + 2 * XB;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -68,8 +48,8 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
   };
   const unsigned clip_bytes = (unsigned)C * (unsigned)L * 2u;                 // a clip's image: [C / 32][L][32] bf16
   const __amdgpu_buffer_rsrc_t urs = uni_rsrc(reinterpret_cast<const char *>(uin) + (size_t)b * clip_bytes, clip_bytes);
-  const __amdgpu_buffer_rsrc_t w1rs = uni_rsrc(reinterpret_cast<const char *>(w1) + (size_t)wave * (8 * 6 * 2 * UFR_), 8 * 6 * 2 * UFR_);
-  const __amdgpu_buffer_rsrc_t w2rs = uni_rsrc(reinterpret_cast<const char *>(w2) + (size_t)wave * (2 * 16 * UFR_), 16 * UFR_);   // row tile 0 only
+  const __amdgpu_buffer_rsrc_t w1rs = uni_rsrc(reinterpret_cast<const char *>(w1) + (size_t)wave * (8 * 6 * 2 * BF_FR), 8 * 6 * 2 * BF_FR);
+  const __amdgpu_buffer_rsrc_t w2rs = uni_rsrc(reinterpret_cast<const char *>(w2) + (size_t)wave * (2 * 16 * BF_FR), 16 * BF_FR);   // row tile 0 only
   const unsigned lane16 = (unsigned)lane * 16u;
 
   // ---- GEMM1 staging (pure data movement): thread = (column sj, 16-byte piece so of the 64-byte row); threads 0-255 move taps 0 and 1,
@@ -82,18 +62,18 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
     const int tp = t0 + sj + (tap - 1) * d;
     xv[i] = (tp >= 0 && tp < L && !(sh && i)) ? (unsigned)tp * 64u + (unsigned)so * 16u : 0x80000000u;   // outside the clip: zeros (WaveNet.py:26-27)
   }
-  u32x4v xq[2];
+  u32x4 xq[2];
   auto issue_x = [&](int ch) {
-    xq[0] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(urs, xv[0], ch * L * 64, 0));
-    if (!sh) xq[1] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(urs, xv[1], ch * L * 64, 0));
+    xq[0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, xv[0], ch * L * 64, 0));
+    if (!sh) xq[1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, xv[1], ch * L * 64, 0));
   };
   auto store_x = [&](__bf16 *dst) {
-    __bf16 *row = dst + sj * UXS_ + 8 * so;
+    __bf16 *row = dst + sj * BF_XS + 8 * so;
     if (sh) {
-      *reinterpret_cast<u32x4v *>(row + 64) = xq[0];
+      *reinterpret_cast<u32x4 *>(row + 64) = xq[0];
     } else {
-      *reinterpret_cast<u32x4v *>(row) = xq[0];
-      *reinterpret_cast<u32x4v *>(row + 32) = xq[1];
+      *reinterpret_cast<u32x4 *>(row) = xq[0];
+      *reinterpret_cast<u32x4 *>(row + 32) = xq[1];
     }
   };
 
@@ -111,7 +91,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
   auto load_a1 = [&](bf16x8(&a)[2], int step) {
 #pragma unroll
     for (int rt = 0; rt < 2; rt++)
-      a[rt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w1rs, lane16 + rt * UFR_, step * 2 * UFR_, 0));
+      a[rt] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w1rs, lane16 + rt * BF_FR, step * 2 * BF_FR, 0));
   };
   bf16x8 a1[3][2];                                               // ring of three k-steps, requested two ahead (six per chunk: slot = ks % 3)
   load_a1(a1[0], 0);
@@ -121,7 +101,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
   __syncthreads();
 #pragma unroll 1
   for (int ch = 0; ch < 8; ch++) {
-    const __bf16 *xb = lds + (ch & 1) * XB + j * UXS_ + 8 * hh;
+    const __bf16 *xb = lds + (ch & 1) * XB + j * BF_XS + 8 * hh;
     if (ch + 1 < 8) issue_x(ch + 1);
 #pragma unroll
     for (int ks = 0; ks < 6; ks++) {
@@ -129,7 +109,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
       load_a1(a1[(ks + 2) % 3], nx < 48 ? nx : 47);
       bf16x8 bq[2];
 #pragma unroll
-      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(xb + 32 * ct * UXS_ + 16 * ks);
+      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(xb + 32 * ct * BF_XS + 16 * ks);
 #pragma unroll
       for (int rt = 0; rt < 2; rt++)
 #pragma unroll
@@ -143,17 +123,17 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
   // ---- GEMM2's first weight fragments and the residual's rows of u (chunk `wave` of the image: lane (j, hh) of column tile ct takes bytes
   // [32 s + 16 hh, + 16) of row t0 + 32 ct + j -- the values its accumulator registers 8 s .. 8 s + 7 belong to) go out under the gate
   bf16x8 a2[4];
-  u32x4v pre[2][2];
+  u32x4 pre[2][2];
   unsigned ro[2];
   if constexpr (!NOH) {
 #pragma unroll
-    for (int i = 0; i < 3; i++) a2[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, i * UFR_, 0));
+    for (int i = 0; i < 3; i++) a2[i] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, i * BF_FR, 0));
 #pragma unroll
     for (int ct = 0; ct < 2; ct++) {
       const int t = t0 + 32 * ct + j;
       ro[ct] = t < L ? (unsigned)((wave * L + t) * 64 + hh * 16) : 0x80000000u;   // outside the clip: loads 0, store dropped
-      pre[ct][0] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(urs, ro[ct], 0, 0));
-      pre[ct][1] = __builtin_bit_cast(u32x4v, __builtin_amdgcn_raw_buffer_load_b128(urs, ro[ct] + 32u, 0, 0));
+      pre[ct][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, ro[ct], 0, 0));
+      pre[ct][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, ro[ct] + 32u, 0, 0));
     }
   }
 
@@ -167,9 +147,9 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
       for (int e = 0; e < 4; e += 2) {
         const f32x2 a2v = {acc[0][ct][4 * qq + e], acc[0][ct][4 * qq + e + 1]};
         const f32x2 b2v = {acc[1][ct][4 * qq + e], acc[1][ct][4 * qq + e + 1]};
-        pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(gate_pair_us(a2v, b2v), bf16x2));
+        pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(gate_fast2(a2v, b2v), bf16x2));
       }
-      *reinterpret_cast<uint2 *>(gim + (32 * ct + j) * UGS_ + 32 * wave + 8 * qq + 4 * hh) = make_uint2(pk[0], pk[1]);
+      *reinterpret_cast<uint2 *>(gim + (32 * ct + j) * BF_GS + 32 * wave + 8 * qq + 4 * hh) = make_uint2(pk[0], pk[1]);
     }
   __syncthreads();
 
@@ -181,7 +161,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
     const unsigned off = t < L ? (unsigned)t * 512u + (unsigned)part * 64u : 0x80000000u;     // outside the clip: dropped
 #pragma unroll
     for (int i = 0; i < 4; i++)
-      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4v *>(gim + col * UGS_ + 32 * part + 8 * i), grs, off + 16u * i, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4 *>(gim + col * BF_GS + 32 * part + 8 * i), grs, off + 16u * i, 0, 0);
   }
   if constexpr (NOH) {
     return;                                                      // the net's last layer: no image is written (WaveNet.py:131-135)
@@ -200,13 +180,13 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
         acr[1][4 * q + e] = bv[e];
       }
     }
-    const __bf16 *gb = gim + j * UGS_ + 8 * hh;
+    const __bf16 *gb = gim + j * BF_GS + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < 16; ks++) {
-      if (ks + 3 < 16) a2[(ks + 3) & 3] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, (ks + 3) * UFR_, 0));
+      if (ks + 3 < 16) a2[(ks + 3) & 3] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16, (ks + 3) * BF_FR, 0));
       bf16x8 bq[2];
 #pragma unroll
-      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + 32 * ct * UGS_ + 16 * ks);
+      for (int ct = 0; ct < 2; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + 32 * ct * BF_GS + 16 * ks);
 #pragma unroll
       for (int ct = 0; ct < 2; ct++) acr[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks & 3], bq[ct], acr[ct], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
@@ -220,7 +200,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
 #pragma unroll
       for (int s = 0; s < 2; s++) {
 #pragma clang fp contract(off)                                  // the oracle's operation order: (u + acc) * rs, then + part_t, each rounded to fp32
-        u32x4v o;
+        u32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; e++) {
           const unsigned uw = pre[ct][s][e];

@@ -175,13 +175,13 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_gate_kernel(const float *
       float yt[16], ys[16];
 #pragma unroll
       for (int r = 0; r < 16; r++) {
-        const int ro = ((r & 3) + 8 * (r >> 2)) * L * 4;
+        const int ro = rowoff(r, 0) * L * 4;
         yt[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, eo, ro, 0));
         ys[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, eo + half, ro, 0));
       }
 #pragma unroll
       for (int r = 0; r < 16; r++) {
-        const int ro = ((r & 3) + 8 * (r >> 2)) * L * 4;
+        const int ro = rowoff(r, 0) * L * 4;
         const float at = fminf(fmaxf(yt[r], -15.0f), 15.0f);
         const float E = exp_acc(2.0f * at), F = exp_acc(-fmaxf(ys[r], -80.0f));
         const float R = __builtin_amdgcn_rcpf((E + 1.0f) * (1.0f + F));
@@ -360,13 +360,13 @@ __global__ __launch_bounds__(256, 1) void resblock_bwd_conv_kernel(const float *
         float r0[16], r1[16];
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int ro = ((r & 3) + 8 * (r >> 2)) * L * 4;
+          const int ro = rowoff(r, 0) * L * 4;
           r0[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, e0, ro, 0));
           r1[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, e1, ro, 0));
         }
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          const int ro = ((r & 3) + 8 * (r >> 2)) * L * 4;
+          const int ro = rowoff(r, 0) * L * 4;
           const float y0 = (acc[0][rt][ct][r] + acc[1][rt][ct][r]) + acc[2][rt][ct][r];
           const float y1 = (acc[1][rt][ct][r] - acc[2][rt][ct][r]) + acc[3][rt][ct][r];
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, __builtin_fmaf(RS, r0[r], y0)), ors, e0, ro, 0);
@@ -436,9 +436,7 @@ int prepare_bwd_f32(ap_ctx *ctx, hipStream_t st) {
 
 extern "C" int ap_resblock_bwd(ap_ctx *ctx, int layer, const float *dh_out, const float *dskip, const float *pre_gate, float *dy_scratch,
                                float *dh_in, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !dh_out || !dskip || !pre_gate || !dy_scratch || !dh_in) { ap::set_error("ap_resblock_bwd: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { ap::set_error("ap_resblock_bwd: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (dh_in == dh_out) { ap::set_error("ap_resblock_bwd: dh_in must not alias dh_out"); return -22; }
+  if (int e = ap::check_block_args("ap_resblock_bwd", ctx, dh_out && dskip && pre_gate && dy_scratch && dh_in, layer, B, L, dh_out, "dh_out", dh_in, "dh_in")) return e;
   return ap::launch_resblock_bwd(ctx, layer, dh_out, dskip, pre_gate, dy_scratch, dh_in, B, L, (hipStream_t)stream);
 }
 

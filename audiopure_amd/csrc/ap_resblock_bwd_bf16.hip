@@ -23,12 +23,7 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4b __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2b __attribute__((ext_vector_type(2)));
 
 constexpr int QC_ = 256;                  // res = skip channels
 constexpr int XSB_ = 96 + 8;              // bf16 per column row of K1's X chunk image (3 taps x 32 channels; 208-byte rows)
@@ -48,7 +43,7 @@ __device__ __forceinline__ unsigned xcd_tile(unsigned k, unsigned G) {
   if (g_bwdb_linear) return k;
 #endif
   const unsigned x = k & 7u, q = G >> 3, r = G & 7u;
-  return x * q + (x < r ? x : r) + (k >> 3);
+  return x * q + (x < r ? x : r) + (k >> 3);                     // = xcd_logical(k, G), kept in this form: calling it changes this file's instructions
 }
 
 __device__ __forceinline__ bf16x8 cvt8(const float (&v)[8]) {
@@ -317,7 +312,7 @@ __global__ __launch_bounds__(512) void resblock_bwd_gate_bf16_kernel(
     const unsigned off = t < L ? (unsigned)t * 1024u + (unsigned)part * 256u : 0x80000000u;
 #pragma unroll
     for (int i = 0; i < 16; i++)
-      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4b *>(lds + col * DSB_ + 128 * part + 8 * i), ors, off + 16u * i, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4 *>(lds + col * DSB_ + 128 * part + 8 * i), ors, off + 16u * i, 0, 0);
   }
 }
 
@@ -374,12 +369,12 @@ __global__ __launch_bounds__(512, 4) void resblock_bwd_gate_fac_bf16_kernel(cons
   const int ts = t0 + sj;
   const unsigned zv = ts < L ? ((unsigned)ts + (unsigned)(RPT * sq) * (unsigned)L) * 4u : 0x80000000u;
   float zr[RPT];
-  u32x4b zq[RPT / 8];
+  u32x4 zq[RPT / 8];
   const unsigned ziv = ts < L ? (unsigned)ts * (unsigned)(C * 2) + (unsigned)(2 * RPT * sq) : 0x80000000u;   // DSI: this thread's RPT channels of the sample's row
   auto issue_z = [&](int kc) {                                   // chunks 0, 1: dh' rows, 2, 3: dskip rows
     if (DSI && kc >= 2) {
 #pragma unroll
-      for (int o = 0; o < RPT / 8; o++) zq[o] = __builtin_bit_cast(u32x4b, __builtin_amdgcn_raw_buffer_load_b128(dsirs, ziv + 16u * o, (kc & 1) * 256, 0));
+      for (int o = 0; o < RPT / 8; o++) zq[o] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(dsirs, ziv + 16u * o, (kc & 1) * 256, 0));
       return;
     }
     const __amdgpu_buffer_rsrc_t rs = uni_rsrc(kc < 2 ? dh_b : ds_b, clip_bytes);
@@ -389,7 +384,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bwd_gate_fac_bf16_kernel(cons
   auto store_z = [&](__bf16 *dst, int kc) {
     if (DSI && kc >= 2) {
 #pragma unroll
-      for (int o = 0; o < RPT / 8; o++) *reinterpret_cast<u32x4b *>(dst + sj * ZSB2_ + RPT * sq + 8 * o) = zq[o];
+      for (int o = 0; o < RPT / 8; o++) *reinterpret_cast<u32x4 *>(dst + sj * ZSB2_ + RPT * sq + 8 * o) = zq[o];
       return;
     }
 #pragma unroll
@@ -402,13 +397,13 @@ __global__ __launch_bounds__(512, 4) void resblock_bwd_gate_fac_bf16_kernel(cons
   };
   issue_z(0);
   // the factors this lane wrote in the forward pass: [128-sample tile][wave][column tile][q][lane] x 16 bytes; in flight under the whole GEMM
-  u32x4b fq[CT][4];
+  u32x4 fq[CT][4];
 #pragma unroll
   for (int ct = 0; ct < CT; ct++)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const int gct = (t0 >> 5) + ct;                            // column tile of the clip: 128-sample tile gct >> 2, its column tile gct & 3
-      fq[ct][q] = __builtin_bit_cast(u32x4b, __builtin_amdgcn_raw_buffer_load_b128(frs, lane16, (((gct >> 2) * 8 + wave) * 16 + (gct & 3) * 4 + q) * 1024, 2));
+      fq[ct][q] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(frs, lane16, (((gct >> 2) * 8 + wave) * 16 + (gct & 3) * 4 + q) * 1024, 2));
     }
 
   f32x16 accg[CT];
@@ -466,7 +461,7 @@ __global__ __launch_bounds__(512, 4) void resblock_bwd_gate_fac_bf16_kernel(cons
     const unsigned off = t < L ? (unsigned)t * 1024u + (unsigned)(part * PB) : 0x80000000u;
 #pragma unroll
     for (int i = 0; i < PB / 16; i++)
-      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4b *>(lds + col * DSB_ + (PB / 2) * part + 8 * i), ors, off + 16u * i, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4 *>(lds + col * DSB_ + (PB / 2) * part + 8 * i), ors, off + 16u * i, 0, 0);
   }
 }
 
@@ -509,15 +504,15 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_conv_bf16_kernel(const __
     const int t = t0 + scol + (tp - 1) * d;
     yv[tp] = (t >= 0 && t < L) ? (unsigned)t * 1024u + (unsigned)spart * (16u * PPT) : 0x80000000u;    // outside the clip: zeros (WaveNet.py:26-27)
   }
-  u32x4b yq[PPT];
+  u32x4 yq[PPT];
   auto issue_y = [&](int ch) {
     const unsigned v = (ch >> 2) == 0 ? yv[0] : (ch >> 2) == 1 ? yv[1] : yv[2];
 #pragma unroll
-    for (int i = 0; i < PPT; i++) yq[i] = __builtin_bit_cast(u32x4b, __builtin_amdgcn_raw_buffer_load_b128(yrs, v, (ch & 3) * 256 + 16 * i, 0));
+    for (int i = 0; i < PPT; i++) yq[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(yrs, v, (ch & 3) * 256 + 16 * i, 0));
   };
   auto store_y = [&](__bf16 *dst) {
 #pragma unroll
-    for (int i = 0; i < PPT; i++) *reinterpret_cast<u32x4b *>(dst + scol * YSB_ + 8 * PPT * spart + 8 * i) = yq[i];
+    for (int i = 0; i < PPT; i++) *reinterpret_cast<u32x4 *>(dst + scol * YSB_ + 8 * PPT * spart + 8 * i) = yq[i];
   };
   f32x16 acc[2][CT];
 #pragma unroll
@@ -586,11 +581,11 @@ __global__ __launch_bounds__(256, 2) void resblock_bwd_conv_bf16_kernel(const __
       const unsigned eo = t < L ? ((unsigned)(64 * wave + 32 * rt + 4 * hh) * (unsigned)L + (unsigned)t) * 4u : 0x80000000u;
       float rv[16];
 #pragma unroll
-      for (int r = 0; r < 16; r++) rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 0));
+      for (int r = 0; r < 16; r++) rv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prs, eo, rowoff(r, 0) * L * 4, 0));
 #pragma unroll
       for (int r = 0; r < 16; r++)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, __builtin_fmaf(RS, rv[r], acc[rt][ct][r])), ors, eo,
-                                              ((r & 3) + 8 * (r >> 2)) * L * 4, 0);
+                                              rowoff(r, 0) * L * 4, 0);
     }
 }
 
@@ -706,9 +701,7 @@ int prepare_bwd_bf16(ap_ctx *ctx, hipStream_t st) {
 
 extern "C" int ap_resblock_bwd_bf16(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, const float *dh_out,
                                     const float *dskip, void *dy_scratch, float *dh_in, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !h_in || !part_t_layer || !dh_out || !dskip || !dy_scratch || !dh_in) { ap::set_error("ap_resblock_bwd_bf16: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { ap::set_error("ap_resblock_bwd_bf16: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (dh_in == dh_out) { ap::set_error("ap_resblock_bwd_bf16: dh_in must not alias dh_out"); return -22; }
+  if (int e = ap::check_block_args("ap_resblock_bwd_bf16", ctx, h_in && part_t_layer && dh_out && dskip && dy_scratch && dh_in, layer, B, L, dh_out, "dh_out", dh_in, "dh_in")) return e;
   return ap::launch_resblock_bwd_bf16(ctx, layer, h_in, part_t_layer, dh_out, dskip, dy_scratch, dh_in, B, L, (hipStream_t)stream);
 }
 
@@ -720,9 +713,7 @@ extern "C" int ap_bwd_bf16_rows_image(const float *rows, void *image, int B, int
 
 extern "C" int ap_resblock_bwd_bf16_saved(ap_ctx *ctx, int layer, const void *gate_factors, const float *dh_out, const void *dskip,
                                           int dskip_is_image, void *dy_scratch, float *dh_in, int B, int L, void *stream) {
-  if (!ctx || !ctx->loaded || !gate_factors || !dh_out || !dskip || !dy_scratch || !dh_in) { ap::set_error("ap_resblock_bwd_bf16_saved: not loaded / null"); return -22; }
-  if (layer < 0 || layer >= ctx->NL || B < 1 || L < 1) { ap::set_error("ap_resblock_bwd_bf16_saved: layer=%d B=%d L=%d", layer, B, L); return -22; }
-  if (dh_in == dh_out) { ap::set_error("ap_resblock_bwd_bf16_saved: dh_in must not alias dh_out"); return -22; }
+  if (int e = ap::check_block_args("ap_resblock_bwd_bf16_saved", ctx, gate_factors && dh_out && dskip && dy_scratch && dh_in, layer, B, L, dh_out, "dh_out", dh_in, "dh_in")) return e;
   return ap::launch_resblock_bwd_bf16_saved(ctx, layer, gate_factors, dh_out, dskip, dskip_is_image, dy_scratch, dh_in, B, L, (hipStream_t)stream);
 }
 

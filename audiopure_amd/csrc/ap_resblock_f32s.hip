@@ -18,68 +18,12 @@
 
 namespace ap {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 namespace f32s {
 constexpr int BT = 128;                  // time tile
 constexpr int BKC = 16;                  // channels per staged chunk -> 48 K rows = 3 k-steps (one per tap)
 constexpr int XS = 3 * BKC + 8;          // bf16 per column row of an X image (112 B: conflict-free b128 reads)
 constexpr int HT = 64;                   // columns per gate/GEMM2 half
 constexpr int PSTR = 32;                 // fp32 row stride of the wave-private output patch (128-B rows: conflict-free for the column writes and the 16-lane groups of the b128 row reads; 144-B rows were 2-way)
-
-__device__ __forceinline__ int rowoff_s(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-__device__ __forceinline__ float bf_up(__bf16 v) { return (float)v; }
-
-// x = p[0] + p[1] + p[2] exactly (fp32 has 24 mantissa bits, each part carries 8)
-__device__ __forceinline__ void split3(float x, __bf16 (&p)[3]) {
-  p[0] = (__bf16)x;
-  const float r1 = x - bf_up(p[0]);
-  p[1] = (__bf16)r1;
-  const float r2 = r1 - bf_up(p[1]);
-  p[2] = (__bf16)r2;
-}
-
-// four values at once, written so the conversions lower to v_cvt_pk_bf16_f32 (two per instruction) and the
-// widenings to one shift / mask: 11 VALU per pair instead of ~20
-typedef unsigned int u32x2s __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3x4(const float (&x)[4], u32x2s (&out)[3]) {
-#pragma unroll
-  for (int pr = 0; pr < 2; pr++) {
-    float v0 = x[2 * pr], v1 = x[2 * pr + 1];
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
-      out[s][pr] = pk;
-      if (s < 2) {
-        v0 -= __builtin_bit_cast(float, pk << 16);
-        v1 -= __builtin_bit_cast(float, pk & 0xffff0000u);
-      }
-    }
-  }
-}
-
-// same compensated exp and gate as the fp32 kernel (ap_kernels.hip) -- the gate is not where the two modes differ
-__device__ __forceinline__ float exp_acc_s(float x) {
-  const float L2E_HI = 1.44269502162933349609375f;
-  const float L2E_LO = 1.92596299e-8f;
-  float t = x * L2E_HI;
-  float r = __builtin_fmaf(x, L2E_HI, -t);
-  r = __builtin_fmaf(x, L2E_LO, r);
-  float e = __builtin_amdgcn_exp2f(t);
-  return __builtin_fmaf(e, r * 0.693147182464599609375f, e);
-}
-__device__ __forceinline__ float gate_s(float a, float b) {
-  a = fminf(fmaxf(a, -15.0f), 15.0f);
-  b = fmaxf(b, -80.0f);
-  float E = exp_acc_s(2.0f * a);
-  float F = exp_acc_s(-b);
-  return (E - 1.0f) * __builtin_amdgcn_rcpf((E + 1.0f) * (1.0f + F));
-}
 }  // namespace f32s
 using namespace f32s;
 
@@ -142,8 +86,6 @@ int launch_pack_split(ap_ctx *ctx, hipStream_t st) {
 }
 
 // ---- the kernel ---------------------------------------------------------------------------------------------
-// the six partial products kept, as (weight split, activation split)
-#define AP_SPLIT_TERMS(F) F(0, 0) F(0, 1) F(1, 0) F(0, 2) F(2, 0) F(1, 1)
 
 template <int C, bool E4, bool TRACE>
 __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
@@ -175,7 +117,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
     }
   };
   mark(0);
-  int b_, tile_;                                               // XCD-local walk (ap_common.h; speed only)
+  int b_, tile_;                                               // XCD-local walk (ap_device.h; speed only)
   ap_tile_of_block(blockIdx.x, nblk, ntiles, d, BT, b_, tile_);
   const int b = __builtin_amdgcn_readfirstlane(b_);
   const int t0 = __builtin_amdgcn_readfirstlane(tile_ * BT);
@@ -232,11 +174,11 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
       float u[4];
 #pragma unroll
       for (int e = 0; e < 4; e++) u[e] = tok[tap] ? xr[tap][e] + pte[e] : 0.f;
-      u32x2s pk[3];
+      u32x2 pk[3];
       split3x4(u, pk);
 #pragma unroll
       for (int s = 0; s < 3; s++)
-        *reinterpret_cast<u32x2s *>(dst + s * XIMG + (col * XS + tap * BKC + q4) * 2) = pk[s];
+        *reinterpret_cast<u32x2 *>(dst + s * XIMG + (col * XS + tap * BKC + q4) * 2) = pk[s];
     }
   };
 
@@ -367,12 +309,12 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
       for (int qq = 0; qq < 4; qq++) {
         float gv[4];
 #pragma unroll
-        for (int e = 0; e < 4; e++) gv[e] = gate_s(acc[0][ct][4 * qq + e], acc[1][ct][4 * qq + e]);
-        u32x2s pk[3];
+        for (int e = 0; e < 4; e++) gv[e] = gate(acc[0][ct][4 * qq + e], acc[1][ct][4 * qq + e]);
+        u32x2 pk[3];
         split3x4(gv, pk);
 #pragma unroll
         for (int s = 0; s < 3; s++)
-          *reinterpret_cast<u32x2s *>(lds + s * GIMG + ((32 * c2 + j) * GS + 32 * wave + 8 * qq + 4 * hh) * 2) = pk[s];
+          *reinterpret_cast<u32x2 *>(lds + s * GIMG + ((32 * c2 + j) * GS + 32 * wave + 8 * qq + 4 * hh) * 2) = pk[s];
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -408,7 +350,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
 #pragma unroll
           for (int r = 0; r < 16; r++)
             pre[c2][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                       pass == 0 ? hrs : srs, evoff[c2], ((r & 3) + 8 * (r >> 2)) * L * 4, 2));   // nt: once-touched skip rows; the residual re-read of h hits or passes without allocating
+                                                       pass == 0 ? hrs : srs, evoff[c2], rowoff(r, 0) * L * 4, 2));   // nt: once-touched skip rows; the residual re-read of h hits or passes without allocating
         }
       }
       f32x16 ac[2];
@@ -471,7 +413,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
       for (int c2 = 0; c2 < 2; c2++) {
         if constexpr (E4) {
 #pragma unroll
-          for (int r = 0; r < 16; r++) patch[rowoff_s(r, hh) * PSTR + j] = ac[c2][r];
+          for (int r = 0; r < 16; r++) patch[rowoff(r, hh) * PSTR + j] = ac[c2][r];
 #pragma unroll
           for (int p = 0; p < 4; p++) {
             const float4 v = *reinterpret_cast<const float4 *>(patch + ((lane >> 3) + 8 * p) * PSTR + 4 * (lane & 7));
@@ -489,7 +431,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
           for (int r = 0; r < 16; r++)
             __builtin_amdgcn_raw_buffer_store_b32(
                 __builtin_bit_cast(unsigned, (add ? pre[c2][r] + ac[c2][r] : ac[c2][r]) * scale), pass == 0 ? ors : srs,
-                evoff[c2], ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
+                evoff[c2], rowoff(r, 0) * L * 4, 2);
         }
       }
     };

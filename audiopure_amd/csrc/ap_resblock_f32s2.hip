@@ -35,12 +35,6 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int C2_ = 256;                 // res = skip channels
 constexpr int NPT_ = 64;                 // pairs per K1 tile (128 outputs)
 constexpr int KC1_ = 32;                 // input channels per K1 chunk: 4 products x 32 = 128 K rows = 8 k-steps (96 MFMAs per wave: a chunk
@@ -53,41 +47,6 @@ constexpr int KC2_ = 64;                 // g channels per K2 chunk = 4 k-steps 
 constexpr int XS2_ = KC2_ + 8;           // bf16 per column row of a K2 g image (144 B: conflict-free ds_read_b128)
 constexpr int XIMG2_ = BT2_ * XS2_ * 2;  // 18,432 B per split image
 constexpr int XBUF2_ = 3 * XIMG2_;
-
-// four values -> three bf16 parts each (x = p0 + p1 + p2 exactly), packed two per dword (ap_resblock_f32s.hip: split3x4)
-__device__ __forceinline__ void split3x4_(const float (&x)[4], u32x2 (&out)[3]) {
-#pragma unroll
-  for (int pr = 0; pr < 2; pr++) {
-    float v0 = x[2 * pr], v1 = x[2 * pr + 1];
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v0, v1}, bf16x2));
-      out[s][pr] = pk;
-      if (s < 2) {
-        v0 -= __builtin_bit_cast(float, pk << 16);
-        v1 -= __builtin_bit_cast(float, pk & 0xffff0000u);
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ void split3_(float x, __bf16 (&p)[3]) {
-  p[0] = (__bf16)x;
-  const float r1 = x - (float)p[0];
-  p[1] = (__bf16)r1;
-  p[2] = (__bf16)(r1 - (float)p[1]);
-}
-
-// the fp32 kernels' compensated exp and gate (ap_common.h): the gate is not where the arithmetic modes differ
-__device__ __forceinline__ float gate_(float a, float b) { return gate(a, b); }
-
-// the six partial products kept, as (weight split, activation split)
-#define AP_SPLIT_TERMS2(F) F(0, 0) F(0, 1) F(1, 0) F(0, 2) F(2, 0) F(1, 1)
-
-__device__ __forceinline__ void block_to_tile(int bid, int nblk, int &logical) {   // XCD-contiguous runs (placement only)
-  const int xcd = bid & 7, idx = bid >> 3, q = nblk >> 3, r = nblk & 7;
-  logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
 
 }  // namespace
 
@@ -110,7 +69,7 @@ __global__ void pack_w1_split23_kernel(const float *__restrict__ w1f, __bf16 *__
   const double w0 = p[0], w1 = p[1], w2 = p[2];
   const double v = prod == 0 ? w0 : prod == 1 ? (w0 + w1 + w2) * 0.5 : prod == 2 ? (w0 - w1 + w2) * 0.5 : w2;
   __bf16 sp[3];
-  split3_((float)v, sp);
+  split3((float)v, sp);
   const size_t frag = ((((((size_t)half * 8 + w) * (C / KC1_) + ch) * 4 + prod) * 2 + kh) * 3);
 #pragma unroll
   for (int s = 0; s < 3; s++) out[((frag + s) * 64 + lane) * 8 + jj] = sp[s];
@@ -136,8 +95,7 @@ __global__ __launch_bounds__(512, 2) void f32s_gate_kernel(const float *__restri
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, hh = lane >> 5;
   const int d = 1 << logd;
-  int logical;
-  block_to_tile(blockIdx.x, nblk, logical);
+  const int logical = xcd_logical(blockIdx.x, nblk);
   const int half = __builtin_amdgcn_readfirstlane(logical & 1);
   const int b = __builtin_amdgcn_readfirstlane((logical >> 1) / ntiles);
   const int p0 = __builtin_amdgcn_readfirstlane(((logical >> 1) % ntiles) * NPT_);
@@ -220,7 +178,7 @@ __global__ __launch_bounds__(512, 2) void f32s_gate_kernel(const float *__restri
     {
       const float a0_[4] = {da[0], da[1], da[2], da[3]}, a1_[4] = {da[4], da[5], da[6], da[7]};
       const float b0_[4] = {db[0], db[1], db[2], db[3]}, b1_[4] = {db[4], db[5], db[6], db[7]};
-      split3x4_(a0_, pa0); split3x4_(a1_, pa1); split3x4_(b0_, pb0); split3x4_(b1_, pb1);
+      split3x4(a0_, pa0); split3x4(a1_, pa1); split3x4(b0_, pb0); split3x4(b1_, pb1);
     }
 #pragma unroll
     for (int s = 0; s < 3; s++) {
@@ -267,12 +225,12 @@ __global__ __launch_bounds__(512, 2) void f32s_gate_kernel(const float *__restri
       read_b(bx1, xb, ks, 1);
       AP_SB();
 #define AP_T(i, jx) acc[pr][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks & 3][i], bx0[jx], acc[pr][0], 0, 0, 0);
-      AP_SPLIT_TERMS2(AP_T)
+      AP_SPLIT_TERMS(AP_T)
 #undef AP_T
       if constexpr (ks < 7) read_b(bx0, xb, ks + 1, 0);
       AP_SB();
 #define AP_T(i, jx) acc[pr][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks & 3][i], bx1[jx], acc[pr][1], 0, 0, 0);
-      AP_SPLIT_TERMS2(AP_T)
+      AP_SPLIT_TERMS(AP_T)
 #undef AP_T
       if constexpr (ks == 7) store_chunk(nb, ch + 1 < NCH ? ch + 1 : NCH - 1);   // (after the last chunk: a harmless re-store into the idle buffer)
       AP_SB();
@@ -294,14 +252,14 @@ __global__ __launch_bounds__(512, 2) void f32s_gate_kernel(const float *__restri
     const unsigned o0 = ok0 ? (unsigned)tf * 4u : 0x80000000u, o1 = ok1 ? (unsigned)(tf + d) * 4u : 0x80000000u;   // outside: store dropped
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-      const int cg = 128 * half + 16 * wave + (r & 3) + 8 * (r >> 2) + 4 * hh;
+      const int cg = 128 * half + 16 * wave + rowoff(r, hh);
       const float yt0 = (acc[0][ct][r] + acc[1][ct][r]) + acc[2][ct][r];
       const float ys0 = (acc[0][ct][r + 8] + acc[1][ct][r + 8]) + acc[2][ct][r + 8];
       const float yt1 = (acc[1][ct][r] - acc[2][ct][r]) + acc[3][ct][r];
       const float ys1 = (acc[1][ct][r + 8] - acc[2][ct][r + 8]) + acc[3][ct][r + 8];
       const unsigned row = (unsigned)cg * (unsigned)L * 4u;
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gate_(yt0, ys0)), grs, o0 + (ok0 ? row : 0u), 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gate_(yt1, ys1)), grs, o1 + (ok1 ? row : 0u), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gate(yt0, ys0)), grs, o0 + (ok0 ? row : 0u), 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, gate(yt1, ys1)), grs, o1 + (ok1 ? row : 0u), 0, 0);
     }
   }
 }
@@ -316,8 +274,7 @@ __global__ __launch_bounds__(512, 2) void f32s_out_kernel(const float *__restric
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, hh = lane >> 5;
-  int logical;
-  block_to_tile(blockIdx.x, nblk, logical);
+  const int logical = xcd_logical(blockIdx.x, nblk);
   const int b = __builtin_amdgcn_readfirstlane(logical / ntiles);
   const int t0 = __builtin_amdgcn_readfirstlane((logical % ntiles) * BT2_);
   const unsigned clip_bytes = (unsigned)C * (unsigned)L * 4u;
@@ -367,8 +324,8 @@ __global__ __launch_bounds__(512, 2) void f32s_out_kernel(const float *__restric
     for (int o = 0; o < 2; o++) {
       u32x2 lo[3], hi[3];
       const float a[4] = {xr[8 * o + 0], xr[8 * o + 1], xr[8 * o + 2], xr[8 * o + 3]}, c[4] = {xr[8 * o + 4], xr[8 * o + 5], xr[8 * o + 6], xr[8 * o + 7]};
-      split3x4_(a, lo);
-      split3x4_(c, hi);
+      split3x4(a, lo);
+      split3x4(c, hi);
 #pragma unroll
       for (int s = 0; s < 3; s++)
         *reinterpret_cast<u32x4 *>(dst + s * XIMG2_ + (col * XS2_ + o8 + 8 * o) * 2) = u32x4{lo[s][0], lo[s][1], hi[s][0], hi[s][1]};
@@ -395,7 +352,7 @@ __global__ __launch_bounds__(512, 2) void f32s_out_kernel(const float *__restric
 #pragma unroll
       for (int pass = 0; pass < 2; pass++) {
 #define AP_T(i, jx) acc[pass][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[pass][i], bv[jx], acc[pass][ct], 0, 0, 0);
-        AP_SPLIT_TERMS2(AP_T)
+        AP_SPLIT_TERMS(AP_T)
 #undef AP_T
       }
     }
@@ -440,13 +397,13 @@ __global__ __launch_bounds__(512, 2) void f32s_out_kernel(const float *__restric
     float hv[16], sv[16];
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      hv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 2));
-      sv[r] = accumulate ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 2)) : 0.f;
+      hv[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, eo, rowoff(r, 0) * L * 4, 2));
+      sv[r] = accumulate ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(srs, eo, rowoff(r, 0) * L * 4, 2)) : 0.f;
     }
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (hv[r] + acc[0][ct][r]) * RS), grs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv[r] + acc[1][ct][r]), srs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (hv[r] + acc[0][ct][r]) * RS), grs, eo, rowoff(r, 0) * L * 4, 2);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sv[r] + acc[1][ct][r]), srs, eo, rowoff(r, 0) * L * 4, 2);
     }
   }
 }

@@ -323,7 +323,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
             v1[e] = gate(tb, sb);
             if constexpr (SAVE) {                                // channel 64 wave + 32 p + rowoff(r, hh), samples of this lane's pair
               const unsigned so = ((unsigned)(64 * wave + 32 * p + 4 * hh) * (unsigned)L) * 4u;
-              const int ro = ((r & 3) + 8 * (r >> 2)) * L * 4;
+              const int ro = rowoff(r, 0) * L * 4;
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ta), ars, so + sv0, ro, 0);
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sa), ars, so + sv0 + (unsigned)C * (unsigned)L * 4u, ro, 0);
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, tb), ars, so + sv1, ro, 0);
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
           const unsigned ev = ((unsigned)(64 * wave + 32 * rt + 4 * hh) * (unsigned)L + (unsigned)min(tcol[ct], L - 1)) * 4u;
 #pragma unroll
           for (int r = 0; r < 16; r++)
-            hres[rt][ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, ev, ((r & 3) + 8 * (r >> 2)) * L * 4, 2));
+            hres[rt][ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, ev, rowoff(r, 0) * L * 4, 2));
         }
     }
     __syncthreads();                                             // g image complete
@@ -513,16 +513,16 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
               // nt (also the skip store below): once-written streams must not displace the h rows in the XCD's L2, which
               // neighbouring tiles' taps and the residual read again
               __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (hres[rt & 1][ct][r] + acc2[rt][ct][r]) * RS), ors, eo,
-                                                    ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
+                                                    rowoff(r, 0) * L * 4, 2);
           } else if (accumulate) {
 #pragma unroll
             for (int r = 0; r < 16; r++)
-              (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc2[rt][ct][r], srs, (int)eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 0);
+              (void)__builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(acc2[rt][ct][r], srs, (int)eo, rowoff(r, 0) * L * 4, 0);
           } else {
             const u32x16 av = __builtin_bit_cast(u32x16, acc2[rt][ct]);   // (the whole vector, then index: element-wise bit_cast of a vector element mis-folds to a splat)
 #pragma unroll
             for (int r = 0; r < 16; r++)
-              __builtin_amdgcn_raw_buffer_store_b32(av[r], srs, eo, ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
+              __builtin_amdgcn_raw_buffer_store_b32(av[r], srs, eo, rowoff(r, 0) * L * 4, 2);
           }
         }
       }

@@ -27,14 +27,9 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SPT = 128;                  // time tile
 constexpr int SGS = 256 + 8;              // bf16 per column row of the g image in LDS (528 B)
 constexpr int SPS = 32;                   // fp32 per row of the wave-private output patch (128 B)
-
-__device__ __forceinline__ int srowoff(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 }  // namespace
 
@@ -228,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void skipgemm_bf16_kernel(
 #pragma unroll
     for (int ct = 0; ct < 4; ct++) {
 #pragma unroll
-      for (int r = 0; r < 16; r++) patch[srowoff(r, hh) * SPS + j] = acc[ct][r];
+      for (int r = 0; r < 16; r++) patch[rowoff(r, hh) * SPS + j] = acc[ct][r];
 #pragma unroll
       for (int p = 0; p < 4; p++) {
         const float4 v = *reinterpret_cast<const float4 *>(patch + ((lane >> 3) + 8 * p) * SPS + 4 * (lane & 7));

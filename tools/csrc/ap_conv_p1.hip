@@ -22,10 +22,6 @@
 
 namespace ap {
 
-namespace {
-typedef unsigned int u32x4p __attribute__((ext_vector_type(4)));
-}
-
 // grid: (column blocks of 256, row blocks of 256); 4 waves = 2 row halves x 2 column halves.  Cout % 128 == 0, Cin % 8 == 0, HW % 4 == 0.
 // xbytes / obytes: byte sizes of the tensors x / out (and res) live in (below 2^31: buffer descriptors).
 __global__ __launch_bounds__(256, 1) void conv1x1_stream_kernel(const float *__restrict__ x, const float *__restrict__ afrag,
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void conv1x1_stream_kernel(const float *__r
     asm volatile("" : "+a"(acc[rt][0]), "+a"(acc[rt][1]), "+a"(acc[rt][2]), "+a"(acc[rt][3]));
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-      const int row = 32 * rt + (r & 3) + 8 * (r >> 2);          // (+ 4 h: in ov)
+      const int row = 32 * rt + rowoff(r, 0);          // (+ 4 h: in ov)
       const unsigned off = ov + (unsigned)row * (unsigned)HW * 4u;
       f32x4 v = {acc[rt][0][r], acc[rt][1][r], acc[rt][2][r], acc[rt][3][r]};
       if (bias) {
@@ -135,7 +131,7 @@ __global__ __launch_bounds__(256, 1) void conv1x1_stream_kernel(const float *__r
       if (relu) {
         v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f);
       }
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4p, v), ors, off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, off, 0, 0);
     }
   }
 }

@@ -10,18 +10,9 @@
 
 namespace ap {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
 constexpr int BT = 128;                 // time tile
 constexpr int BKC = 32;                 // channels per staged chunk -> 96 K rows = 6 k-steps of 16
 constexpr int XSTRIDE = 3 * BKC + 8;    // bf16 elements per column row of the X image (208 B: conflict-free b128 reads)
-
-__device__ __forceinline__ int rowoff_b(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // tanh(a) sigmoid(b) = (1 - E) / ((1 + E)(1 + F)), E = e^(-2a), F = e^(-b); plain hardware exp2 / rcp are ample next to bf16
 // operand rounding (2^-9).  a is clamped to [-16, 16] first (tanh(+-16) rounds to +-1 in fp32: no result changes), so E stays
@@ -78,7 +69,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_bf16_kernel(
   mark(0);
   // XCD-local order: blocks b, b+8, b+16, ... share an XCD (round-robin dispatch); give each XCD a contiguous run of
   // (clip, tile) work so the +-d taps and the residual patch of a clip are re-read from that XCD's L2.
-  int b_, tile_;                                               // XCD-local walk (ap_common.h; speed only)
+  int b_, tile_;                                               // XCD-local walk (ap_device.h; speed only)
   ap_tile_of_block(blockIdx.x, nblk, ntiles, d, BT, b_, tile_);
   const int b = __builtin_amdgcn_readfirstlane(b_);
   const int t0 = __builtin_amdgcn_readfirstlane(tile_ * BT);
@@ -315,8 +306,6 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_bf16_kernel(
         acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[rt][ct], 0, 0, 0);
       }
     };
-    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
     // k-step 0 (gaps 0-7): weight loads of the next set, B fragments of k-step 1
 #pragma unroll
     for (int m = 0; m < 8; m++) {
@@ -499,7 +488,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_bf16_kernel(
 #pragma unroll
           for (int r = 0; r < 16; r++)
             pre[ct][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                       pass == 0 ? hrs : srs, evoff[ct], ((r & 3) + 8 * (r >> 2)) * L * 4, 2));   // nt: once-touched skip rows; the residual re-read of h hits or passes without allocating
+                                                       pass == 0 ? hrs : srs, evoff[ct], rowoff(r, 0) * L * 4, 2));   // nt: once-touched skip rows; the residual re-read of h hits or passes without allocating
         }
       }
     }
@@ -555,7 +544,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_bf16_kernel(
         if constexpr (E4) {
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            if constexpr (!(DBG & 512)) patch[rowoff_b(r, hh) * PSTR + j] = ac[ct][r];
+            if constexpr (!(DBG & 512)) patch[rowoff(r, hh) * PSTR + j] = ac[ct][r];
           }
 #pragma unroll
           for (int p = 0; p < 4; p++) {
@@ -578,7 +567,7 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_bf16_kernel(
           for (int r = 0; r < 16; r++)
             __builtin_amdgcn_raw_buffer_store_b32(
                 __builtin_bit_cast(unsigned, ((add ? pre[ct][r] : 0.f) + ac[ct][r]) * scale), pass == 0 ? ors : srs,
-                evoff[ct], ((r & 3) + 8 * (r >> 2)) * L * 4, 2);
+                evoff[ct], rowoff(r, 0) * L * 4, 2);
         }
       }
     }

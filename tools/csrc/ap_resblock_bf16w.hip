@@ -32,34 +32,9 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int PT_ = 128;                 // time tile
 constexpr int KC_ = 32;                  // channels per staged chunk -> 96 K rows = 6 k-steps of 16
-constexpr int XS_ = 3 * KC_ + 8;         // bf16 per column row of the X image (208 B)
-constexpr int GS_ = 256 + 8;             // bf16 per column row of the g image (528 B)
 constexpr int PS_ = 32;                  // fp32 per row of the wave-private output patch (128 B)
-
-
-// the gate of ap_resblock_bf16p.hip, element for element (bit-identical kernels)
-__device__ __forceinline__ f32x2 gate_fast2(f32x2 a, f32x2 b) {
-  const f32x2 ac = {__builtin_amdgcn_fmed3f(a[0], -16.0f, 16.0f), __builtin_amdgcn_fmed3f(a[1], -16.0f, 16.0f)};
-  const f32x2 ea = ac * -2.885390081777926815f;
-  const f32x2 eb = b * -1.442695040888963407f;
-  const f32x2 E = {__builtin_amdgcn_exp2f(ea[0]), __builtin_amdgcn_exp2f(ea[1])};
-  const f32x2 F = {__builtin_amdgcn_exp2f(eb[0]), __builtin_amdgcn_exp2f(eb[1])};
-  const f32x2 den = (E + 1.0f) * (F + 1.0f);
-  const f32x2 r = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
-  return (1.0f - E) * r;
-}
-
-using I0 = std::integral_constant<int, 0>;
-using I1 = std::integral_constant<int, 1>;
-using I2 = std::integral_constant<int, 2>;
-using I3 = std::integral_constant<int, 3>;
 
 }  // namespace
 
@@ -77,9 +52,9 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
     int L, int d, int accumulate, int ntiles, int nblk) {
   constexpr int C = 256, NW = 4, NCH = C / KC_, NKS = C / 16;
   constexpr int NT = 2;                                         // nt cache policy on the once-touched streams (see bf16p)
-  constexpr int XBYTES = PT_ * XS_ * 2;                         // 26,624 B per X buffer, two buffers
+  constexpr int XBYTES = PT_ * BF_XS * 2;                         // 26,624 B per X buffer, two buffers
   constexpr int GOFF = 2 * XBYTES;
-  constexpr int POFF = GOFF + PT_ * GS_ * 2;                    // output patches: 4 waves x 32 x 32 fp32
+  constexpr int POFF = GOFF + PT_ * BF_GS * 2;                    // output patches: 4 waves x 32 x 32 fp32
   constexpr int PTOFF = POFF + NW * 32 * PS_ * 4;               // part_t (C floats)
   constexpr int BOFF = PTOFF + C * 4;                           // b1 (2C floats), b2 (2C floats)
   constexpr int LDS_BYTES = BOFF + 4 * C * 4;
@@ -146,7 +121,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
   // channels of one column; the sixteen lanes of a ds_write_b64 group cover all 32 banks).  d % 4 == 0 and L % 4 == 0: a
   // column quad is inside the clip or outside it as a whole, the address is clamped.
   const int q8 = lane & 7, cg = wave * 8 + (lane >> 3);
-  const unsigned xwb = (unsigned)(4 * cg * (XS_ * 2) + ((q8 * 8) ^ ((__builtin_popcount(cg & 7) & 1) << 5)));   // + tap * 64 + sample * 208
+  const unsigned xwb = (unsigned)(4 * cg * (BF_XS * 2) + ((q8 * 8) ^ ((__builtin_popcount(cg & 7) & 1) << 5)));   // + tap * 64 + sample * 208
   // Two register sets: chunk c lives in set c & 1 from its request (during chunk c - 3) to its pack (during chunk c - 1) -- eleven
   // k-steps of sixteen MFMAs between a request and its first use, where one set allowed five: with ONE wave per SIMD a k-step
   // takes half the time it took the eight-wave kernels, and an HBM miss does not.
@@ -197,7 +172,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
     for (int e2 = 0; e2 < 2; e2++)
       pk[e2] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{xr[T][2 * e2][i] + ptv[2 * e2],
                                                                           xr[T][2 * e2 + 1][i] + ptv[2 * e2 + 1]}, bf16x2)) & xkeep[T];
-    *reinterpret_cast<uint2 *>(dst + xwb + T * (2 * KC_) + i * (XS_ * 2)) = make_uint2(pk[0], pk[1]);
+    *reinterpret_cast<uint2 *>(dst + xwb + T * (2 * KC_) + i * (BF_XS * 2)) = make_uint2(pk[0], pk[1]);
   };
   auto pack_tap = [&](unsigned char *dst, auto set_tag, auto t_tag) {
     pack_piece(dst, set_tag, t_tag, I0{}); pack_piece(dst, set_tag, t_tag, I1{});
@@ -223,9 +198,9 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
     return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
                                           wrs, lane16, w2_off + (((2 * wave + u) * 2 + pass) * NKS + ks) * 1024, 0));
   };
-  const int rdoff = (j * XS_ + 8 * hh) * 2;                     // this lane's B-fragment byte offset inside an X buffer
+  const int rdoff = (j * BF_XS + 8 * hh) * 2;                     // this lane's B-fragment byte offset inside an X buffer
   const int rdsw = (__builtin_popcount((j >> 2) & 7) & 1) * 32;
-  const unsigned char *gb = lds + GOFF + (j * GS_ + 8 * hh) * 2;
+  const unsigned char *gb = lds + GOFF + (j * BF_GS + 8 * hh) * 2;
   float *patch = reinterpret_cast<float *>(lds + POFF) + wave * 32 * PS_;
   const float RS = 0.707106781186547524f;
 
@@ -294,7 +269,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
     mark(2);
 
     auto rdb = [&](bf16x8 &dst, const unsigned char *xbe, const unsigned char *xbo, int ct, int ks) {
-      dst = *reinterpret_cast<const bf16x8 *>(((ks & 1) ? xbo : xbe) + (32 * ct) * (XS_ * 2) + ks * 32);
+      dst = *reinterpret_cast<const bf16x8 *>(((ks & 1) ? xbo : xbe) + (32 * ct) * (BF_XS * 2) + ks * 32);
     };
     // One chunk = six k-steps of sixteen MFMAs, column-tile-major: the four MFMAs of a column tile share its B fragment, which
     // is re-read for the next k-step right behind them.  A k-step's four weight fragments are replaced behind their last
@@ -415,7 +390,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
           const f32x2 g2 = (DBG & 32) ? a2 + b2 : gate_fast2(a2, b2);
           pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
         }
-        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * GS_ + 32 * (2 * wave + u) + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
+        *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + j) * BF_GS + 32 * (2 * wave + u) + 8 * qq + 4 * hh) * 2) = make_uint2(pk[0], pk[1]);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -470,7 +445,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
         }
       bf16x8 bq[4];                                              // g-image B fragments: re-read for the next k-step behind their last MFMA
 #pragma unroll
-      for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (GS_ * 2));
+      for (int ct = 0; ct < 4; ct++) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (BF_GS * 2));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < NKS; ks++) {
@@ -480,7 +455,7 @@ __global__ __launch_bounds__(256, 1) void resblock_bf16w_kernel(
           for (int u = 0; u < 2; u++) {
             if constexpr (DBG & 64) asm volatile("" ::"v"(w2r[ks % R2][u]), "v"(bq[ct]));
             else ac[u][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2r[ks % R2][u], bq[ct], ac[u][ct], 0, 0, 0);
-            if (u == 1 && ks + 1 < NKS) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (GS_ * 2) + (ks + 1) * 32);
+            if (u == 1 && ks + 1 < NKS) bq[ct] = *reinterpret_cast<const bf16x8 *>(gb + (32 * ct) * (BF_GS * 2) + (ks + 1) * 32);
             if (ct == 3) {
               if (ks + R2 < NKS) w2r[ks % R2][u] = ld_w2(pass, ks + R2, u);
               else if (pass == 0) w2r[ks % R2][u] = ld_w2(1, ks + R2 - NKS, u);

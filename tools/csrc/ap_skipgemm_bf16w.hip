@@ -10,14 +10,9 @@ namespace ap {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SPT = 128;                  // time tile
 constexpr int SGS = 256 + 8;              // bf16 per column row of the g image in LDS (528 B)
 constexpr int SPS = 32;                   // fp32 per row of the wave-private output patch (128 B)
-
-__device__ __forceinline__ int srowoff(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 }  // namespace
 
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(512, 2) void skipgemm_bf16w_kernel(
         pre[p] = accumulate ? __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srs, evoff, 8 * p * L * 4, 2)) : z;
       }
 #pragma unroll
-      for (int r = 0; r < 16; r++) patch[srowoff(r, hh) * SPS + j] = acc[ct][r];
+      for (int r = 0; r < 16; r++) patch[rowoff(r, hh) * SPS + j] = acc[ct][r];
 #pragma unroll
       for (int p = 0; p < 4; p++) {
         const float4 v = *reinterpret_cast<const float4 *>(patch + ((lane >> 3) + 8 * p) * SPS + 4 * (lane & 7));
@@ -222,7 +217,6 @@ __global__ __launch_bounds__(512, 2) void skipgemm_bf16w_kernel(
     t0_cur = t0_nxt;
   }
 }
-
 
 int g_skipgemm_wide = -1;                                        // tools/cmp_skipgemm.py: 1 = this kernel
 
