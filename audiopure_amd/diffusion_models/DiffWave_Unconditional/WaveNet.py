@@ -141,9 +141,13 @@ class NativeEngine:
     SKIP_GROUP = 36                                  # one skip GEMM per evaluation of the shipped net: skip is written once, never re-read
     WS_FRACTION = 0.7                                # of the device memory that is free (the current workspace counted as free)
 
+    def deferred_skip_group(self) -> int:
+        """Layers per skip GEMM of the deferred-skip form; 0 where this context has no such form or runs the fused block."""
+        return int(self.skip_group or 0) if self._ds_ok else 0
+
     def _sync_group(self):
         if self._ds_ok:                              # the context's group size and the workspace handed over go together
-            N.check(self.lib.ap_ctx_set_skip_group(self.ctx, int(self.skip_group or 0)), "ap_ctx_set_skip_group")
+            N.check(self.lib.ap_ctx_set_skip_group(self.ctx, self.deferred_skip_group()), "ap_ctx_set_skip_group")
 
     def workspace(self, B: int, L: int, device) -> torch.Tensor:
         self._sync_group()

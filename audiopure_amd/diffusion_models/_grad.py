@@ -11,21 +11,15 @@ with the states x_t check-pointed in the forward pass.  A link's 37 layer inputs
 chain fits a memory budget (``SAVE_BUDGET_BYTES``; 288 GB of HBM hold a PGD batch comfortably) and recomputed otherwise
 (the adjoint's memory/compute trade).
 
-``J_eps^T v`` runs on the HIP library.  Shipped shape (res = skip = 256 channels), fp32: the forward keeps the pre-gate
-activations (``ap_resblock_fwd_save``) and a block's backward is ``ap_resblock_bwd`` -- two fused launches (the gate's
-derivative behind ``W2^T [dh'; dskip]``, then the transposed dilated conv in F(2,3) form with the residual path in its
-epilogue): the forward block's flops, no elementwise glue.  bf16 mode at the same shape: ``ap_resblock_bwd_bf16`` -- two launches per
-layer on the bf16 matrix pipe from the layer inputs (the dilated conv recomputed inside), or -- the default -- ``ap_resblock_bwd_bf16_saved``
-from gate derivative factors the forward kept; bf16-storage mode: the same backward behind ``ap_resblock_fwd_u_save``.  Every other shape / arithmetic mode: the residual blocks'
-forward is the fused kernel (``ap_resblock_fwd``), the three GEMM-shaped backward terms of a block -- the recomputed dilated conv, ``W2^T [dh'; dskip]`` and the transposed
-dilated conv -- are ``ap_conv2d_fwd`` calls in ``AP_CONV_1D`` mode (MFMA conv-as-GEMM, weights streamed as
-fragments), with ``ap_gate_bwd`` / ``ap_relu_outer_bwd`` / ``ap_init_conv_bwd`` between them.  Gradients with respect
+``J_eps^T v`` runs on the HIP library.  Which forward sweep a link runs, what it keeps and which backward reads that is
+decided in one place, ``_link_plan`` (the table of kernels per arithmetic mode is its docstring).  Gradients with respect
 to the network's parameters are not formed (the attack differentiates with respect to the audio only; parameters
 are frozen at evaluation, ``adaptive_attack_eval.py:98-101``).
 """
 from __future__ import annotations
 
 import math
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -33,6 +27,96 @@ from .. import _native as N
 
 _RS = 0.707106781186547524
 _F1D = 0x200                      # AP_CONV_1D
+
+
+class _LinkPlan(NamedTuple):
+    """One link's saving forward, as ``_link_plan`` decides it."""
+    sweep: str                    # "block": ap_resblock_fwd[_save] per layer; "gate": ap_resblock_fwd_gate[_save] on fp32 tensors
+    #                               + ap_skip_gemm per group; "u": ap_resblock_fwd_u_save on u images + ap_skip_gemm per group
+    keeps: Optional[str]          # besides layer inputs: "pre_gate", "gate_factors" or None
+    backward: str                 # what serves the save while the flags stay: "f32", "bf16_saved", "bf16" (see _backward_form) or "composed"
+    slots: int                    # residual-stream slots: NL + 1 (every layer's input), 3 (h_0 + a ping-pong pair) or 1 (h_0; the u pair is the sweep's own)
+    group: int                    # layers per skip GEMM (0 in the "block" sweep)
+    dims: tuple                   # (B, C, S, L, NL, embed_dim_out, gate factor bytes per layer)
+
+    def io(self, n: int):
+        """(slot layer n reads, slot it writes its h' / u_out to); "u" sweep: slots of its pair of u images."""
+        if self.keeps != "gate_factors":
+            return n, n + 1
+        return (n & 1, (n + 1) & 1) if self.sweep == "u" else (0 if n == 0 else 1 + ((n - 1) & 1), 1 + (n & 1))
+
+
+def _backward_form(precision, pre_gate: bool, gate_factors: bool, fused_bf16, bwd_f32_available, bwd_bf16_available) -> str:
+    """Which per-layer backward serves a save holding these things (res = skip = 256 channels wherever *_available says yes):
+    "f32"        ap_resblock_bwd from kept pre-gate activations: the gate's derivative behind W2^T [dh'; dskip], then the transposed
+                 dilated conv in F(2,3) form with the residual path in its epilogue -- the forward block's flops, no glue;
+    "bf16_saved" ap_resblock_bwd_bf16_saved from kept gate derivative factors (bf16 and bf16-storage modes): no recomputation;
+    "bf16"       ap_resblock_bwd_bf16 from the layer inputs, the dilated conv recomputed inside its first kernel;
+    "composed"   every other shape / mode: the recomputed dilated conv (unless pre-gate activations were kept), W2^T [dh'; dskip] and
+                 the transposed dilated conv as ap_conv2d_fwd calls in AP_CONV_1D mode, ap_gate_bwd between them."""
+    if gate_factors:
+        return "bf16_saved"
+    if pre_gate:
+        return "f32" if precision == N.AP_PREC_F32 and bwd_f32_available else "composed"
+    return "bf16" if fused_bf16 and precision == N.AP_PREC_BF16 and bwd_bf16_available else "composed"
+
+
+def _link_plan(precision, C, S, NL, embed_dim_out, B, L, acts, keep_gate_factors, fused_bf16, group, bwd_f32_available,
+               bwd_bf16_available, factor_bytes) -> _LinkPlan:
+    """The one decision per link, from plain values (``group``: NativeEngine.deferred_skip_group(); the two ``*_available`` and
+    ``factor_bytes``: the library's answers for this (B, L)):
+      fp32, C in (64, 256), acts   "block" sweep with ap_resblock_fwd_save, keeps the pre-gate activations (3x the memory; the
+                                   backward skips the dilated conv's recomputation)
+      bf16, factors kept (default) "gate" sweep with ap_resblock_fwd_gate_save, keeps the gate's derivative factors (16.4 MB per
+                                   clip-second and layer) and of the layer inputs only the first
+      bf16 otherwise               "gate" sweep (group > 0: the form ap_eps_fwd runs, same eps bit for bit) or "block" sweep
+      bf16 storage                 "u" sweep, always with factors: no lean form (no fp32 layer inputs exist to recompute from), so
+                                   acts=False gives the full form; a shape without that backward is an error
+      everything else              "block" sweep with ap_resblock_fwd, layer inputs only."""
+    bf16_modes = (N.AP_PREC_BF16, N.AP_PREC_BF16_STORE)
+    group = int(group) if precision in bf16_modes else 0
+    if precision == N.AP_PREC_BF16_STORE:
+        if group <= 0 or not bwd_bf16_available:
+            raise N.NativeError("set_precision('bf16s'): no backward for this shape (res = skip = 256 channels, the deferred-skip form)")
+        sweep, keeps, slots = "u", "gate_factors", 1
+    elif acts and fused_bf16 and keep_gate_factors and group > 0 and bwd_bf16_available:
+        sweep, keeps, slots = "gate", "gate_factors", 3
+    else:
+        sweep, slots = "gate" if group > 0 else "block", NL + 1
+        keeps = "pre_gate" if acts and precision == N.AP_PREC_F32 and C in (64, 256) else None
+    form = _backward_form(precision, keeps == "pre_gate", keeps == "gate_factors", fused_bf16, bwd_f32_available, bwd_bf16_available)
+    return _LinkPlan(sweep, keeps, form, slots, group, (B, C, S, L, NL, embed_dim_out, int(factor_bytes)))
+
+
+def _link_buffers(plan: _LinkPlan):
+    """(the buffers a link keeps as [(field of _Saved, shape, dtype)], the gate-image buffer the sweep needs as (shape, dtype) or
+    None): what forward_save allocates and saved_bytes sums.  The gate images live in ONE buffer per EpsGrad, reused by every
+    link (295 MB per clip-second at group = 36)."""
+    B, C, S, L, NL, E, fbytes = plan.dims
+    keep = [("hs", (plan.slots, B, C, L), torch.float32), ("skip", (B, S, L), torch.float32), ("part", (NL * C + E,), torch.float32)]
+    if plan.keeps == "pre_gate":
+        keep.append(("pre_gate", (NL, B, 2 * C, L), torch.float32))
+    if plan.keeps == "gate_factors":
+        keep.append(("gate_factors", (NL, fbytes), torch.uint8))       # (an opaque image per layer)
+    gimg = ((min(plan.group, NL) * B * L * C,), torch.bfloat16) if plan.group > 0 else None
+    return keep, gimg
+
+
+def _nbytes(shape, dtype) -> int:
+    return math.prod(shape) * dtype.itemsize
+
+
+class _Saved(NamedTuple):
+    """What forward_save keeps for backward."""
+    hs: torch.Tensor                                   # [slots][B][C][L] layer inputs (hs[0] = h_0 always)
+    skip: torch.Tensor                                 # [B][S][L] skip sum
+    part: torch.Tensor                                 # FiLM vectors of every layer, then the step embedding
+    pre_gate: Optional[torch.Tensor] = None            # [NL][B][2C][L]
+    gate_factors: Optional[torch.Tensor] = None        # [NL][ap_gate_factor_bytes(B, L)] uint8
+
+    def lean(self) -> "_Saved":
+        """The same evaluation without the pre-gate activations (its backward recomputes the dilated conv)."""
+        return self._replace(pre_gate=None)
 
 
 class EpsGrad:
@@ -106,42 +190,30 @@ class EpsGrad:
         N.check(lib.ap_conv2d_fwd(N.ptr(x), N.ptr(packed), N.ptr(bias), N.ptr(res), N.ptr(out), B, Cin, 1, L, Cout, 1, kw, 1,
                                   pad, 1, fl, Cin, 0, N.stream()), "ap_conv2d_fwd")
 
+    def _plan(self, eng, B, L, acts) -> _LinkPlan:
+        lib, cfg = eng.lib, eng.cfg
+        return _link_plan(self.net._precision, self.C, self.S, self.NL, cfg.embed_dim_out, B, L, acts, self.keep_gate_factors,
+                          self.fused_bf16, eng.deferred_skip_group(), lib.ap_resblock_bwd_available(eng.ctx, B, L),
+                          lib.ap_resblock_bwd_bf16_available(eng.ctx, B, L), lib.ap_gate_factor_bytes(B, L))
+
+    def _ensure_gimg(self, gimg, dev, allocate=True) -> int:
+        """Make the gate-image buffer hold ``gimg`` (of _link_buffers); the bytes newly allocated -- ``allocate=False``: the bytes
+        it would allocate.  The buffer only grows and is reused by every link, so a chain is charged for it once."""
+        if gimg is None or (self._gimg is not None and self._gimg.numel() >= gimg[0][0] and self._gimg.device == dev):
+            return 0
+        if allocate:
+            self._gimg = None
+            self._gimg = torch.empty(gimg[0], device=dev, dtype=gimg[1])
+        return _nbytes(*gimg)
+
     def saved_bytes(self, x: torch.Tensor, acts: bool = True, split: bool = False):
-        """Bytes ``forward_save(x, ., acts)`` keeps, computed without allocating: NL + 1 layer inputs [B][C][L], the skip sum,
-        the FiLM vectors and -- ``acts`` in fp32 arithmetic -- NL pre-gate tensors [B][2C][L]; in bf16 mode also the gate-image
-        buffer of the deferred-skip forward while this object does not hold one of that size yet (it is allocated once and
-        reused by every link, so only the first link is charged for it).  ``split``: the pair (bytes the link keeps, bytes of
-        that one-off buffer) instead of their sum."""
+        """Bytes ``forward_save(x, ., acts)`` keeps, computed without allocating (the sum of _link_buffers), plus the gate-image buffer
+        while this object does not hold one of that size yet.  ``split``: the pair (bytes the link keeps, bytes of that one-off
+        buffer) instead of their sum."""
         eng = self._prepare()
-        B, _, L = x.shape
-        C_, S_, NL = self.C, self.S, self.NL
-        bstore = self.net._precision == N.AP_PREC_BF16_STORE
-        keeps = bstore or (acts and self._keeps_factors(eng, B, L))
-        # (kept factors: layer 0's input + a ping-pong pair; with bf16 storage layer 0's input only -- the u images are the sweep's own)
-        n = ((1 if bstore else 3) if keeps else NL + 1) * B * C_ * L + B * S_ * L + NL * C_ + eng.cfg.embed_dim_out
-        if acts and self.net._precision == N.AP_PREC_F32 and C_ in (64, 256):
-            n += NL * B * 2 * C_ * L
-        extra = 0
-        if keeps:
-            extra += NL * int(eng.lib.ap_gate_factor_bytes(B, L))
-        once = 0
-        G = self._group(eng)
-        if G > 0:
-            need = min(G, NL) * B * L * C_ * 2
-            if self._gimg is None or self._gimg.numel() * 2 < need or self._gimg.device != x.device:
-                once = need
-        return (4 * n + extra, once) if split else 4 * n + extra + once
-
-    def _keeps_factors(self, eng, B, L) -> bool:
-        """bf16 mode at the shipped shape: the forward pass keeps the gate's derivative factors (ap_resblock_fwd_gate_save: 16.4 MB per
-        clip-second and layer) and the backward reads them instead of recomputing the dilated conv (ap_resblock_bwd_bf16_saved)."""
-        return bool(self.fused_bf16 and self.keep_gate_factors and self._group(eng) > 0 and
-                    eng.lib.ap_resblock_bwd_bf16_available(eng.ctx, B, L))
-
-    def _group(self, eng) -> int:
-        """Layers per skip GEMM of forward_save's deferred-skip form (bf16 mode; 0: the fused block per layer)."""
-        return (int(eng.skip_group or 0) if getattr(eng, "_ds_ok", False) and
-                self.net._precision in (N.AP_PREC_BF16, N.AP_PREC_BF16_STORE) else 0)
+        keep, gimg = _link_buffers(self._plan(eng, x.shape[0], x.shape[2], acts))
+        link, once = sum(_nbytes(shape, dtype) for _, shape, dtype in keep), self._ensure_gimg(gimg, x.device, allocate=False)
+        return (link, once) if split else link + once
 
     def eps_only(self, x: torch.Tensor, step: float):
         """The plain fused forward (``ap_eps_fwd``): what the chain's forward pass calls -- nothing is kept."""
@@ -150,104 +222,71 @@ class EpsGrad:
 
     # ---- one eps evaluation, keeping what its backward needs ---------------------------------------------------
     def forward_save(self, x: torch.Tensor, step: float, acts: bool = True):
-        """One eps evaluation that keeps what its backward needs: every layer's input and -- ``acts`` and fp32 arithmetic --
-        every layer's pre-gate activations (``ap_resblock_fwd_save``; 3x the memory, and the backward skips the dilated
-        conv's recomputation)."""
+        """One eps evaluation that keeps what its backward needs: (eps, _Saved).  ``acts=False``: the lean form, layer inputs
+        only, where the mode has one (_link_plan)."""
         eng = self._prepare()
-        lib, dev = eng.lib, x.device
+        lib, ctx, dev, st = eng.lib, eng.ctx, x.device, N.stream()
         B, _, L = x.shape
-        C_, S_, NL = self.C, self.S, self.NL
-        part = torch.empty(NL * C_ + eng.cfg.embed_dim_out, device=dev)
-        N.check(lib.ap_embed(eng.ctx, float(step), N.ptr(part), N.stream()), "ap_embed")
-        if self.net._precision == N.AP_PREC_BF16_STORE:
-            return self._forward_save_bstore(eng, x, step, part)
-        keeps = acts and self._keeps_factors(eng, B, L)
-        # with kept gate factors the backward needs no layer input but the first (ap_init_conv_bwd): hs = [h_0, ping, pong]
-        hs = torch.empty((3 if keeps else NL + 1, B, C_, L), device=dev)
-        src = (lambda n: 0 if n == 0 else 1 + ((n - 1) & 1)) if keeps else (lambda n: n)
-        dst = (lambda n: 1 + (n & 1)) if keeps else (lambda n: n + 1)
-        skip = torch.empty((B, S_, L), device=dev)
-        pre = torch.empty((NL, B, 2 * C_, L), device=dev) if acts and self.net._precision == N.AP_PREC_F32 and C_ in (64, 256) else None
-        N.check(lib.ap_init_conv(eng.ctx, N.ptr(x), N.ptr(hs[0]), B, L, N.stream()), "ap_init_conv")
-        G = self._group(eng)
-        if G > 0:
-            # bf16 mode, the deferred-skip form the chain's own forward runs (ap_resblock_fwd_gate + one ap_skip_gemm per group of G
-            # layers: same grouping, so eps equals ap_eps_fwd's bit for bit); the last layer's h' is not computed (nobody reads it:
-            # hs[NL] stays unwritten and backward() starts from dh = 0).  The gate images live in ONE buffer held by this object
-            # and reused by every link (295 MB per clip-second at G = 36; saved_bytes charges it to the chain's budget once).
-            need = min(G, NL) * B * L * C_
-            if self._gimg is None or self._gimg.numel() < need or self._gimg.device != dev:
-                self._gimg = None
-                self._gimg = torch.empty(need, device=dev, dtype=torch.bfloat16)
-            gimg = self._gimg[:need].view(min(G, NL), B, L, C_)
-            if keeps:
-                pre = torch.empty((NL, int(lib.ap_gate_factor_bytes(B, L))), device=dev, dtype=torch.uint8)   # (rides in the `pre` slot of `saved`)
+        C_, NL = self.C, self.NL
+        plan = self._plan(eng, B, L, acts)
+        keep, gimg = _link_buffers(plan)
+        saved = _Saved(**{name: torch.empty(shape, device=dev, dtype=dtype) for name, shape, dtype in keep})
+        hs, skip, part, pre, fac = saved
+        N.check(lib.ap_embed(ctx, float(step), N.ptr(part), st), "ap_embed")
+        N.check(lib.ap_init_conv(ctx, N.ptr(x), N.ptr(hs[0]), B, L, st), "ap_init_conv")
+        film = lambda n: N.ptr(part[n * C_:(n + 1) * C_])
+        # the deferred-skip sweeps do not compute the last layer's h' / u_out (nobody reads it: hs[NL] stays unwritten and backward()
+        # starts from dh = 0)
+        if plan.sweep == "u":
+            # the sweep ap_eps_fwd runs with bf16 storage (same eps bit for bit), every block also keeping its gate's derivative factors;
+            # the rounding of the stored residual passes the gradient straight through, so the backward is the bf16 mode's
+            u = torch.empty((2, B * C_ * L), device=dev, dtype=torch.bfloat16)   # the residual stream's ping-pong pair of u images
+            N.check(lib.ap_init_conv_u(ctx, N.ptr(x), N.ptr(part[:C_]), u[0].data_ptr(), B, L, st), "ap_init_conv_u")
+
+            def layer(n, g):
+                last = n + 1 == NL
+                src, dst = plan.io(n)
+                N.check(lib.ap_resblock_fwd_u_save(ctx, n, u[src].data_ptr(), None if last else film(n + 1),
+                                                   None if last else u[dst].data_ptr(), g, fac[n].data_ptr(), B, L, st),
+                        "ap_resblock_fwd_u_save")
+        elif plan.sweep == "gate":
+            def layer(n, g):
+                src, dst = plan.io(n)
+                h_in, h_out = N.ptr(hs[src]), N.ptr(hs[dst]) if n + 1 < NL else None
+                if fac is not None:
+                    N.check(lib.ap_resblock_fwd_gate_save(ctx, n, h_in, film(n), h_out, g, fac[n].data_ptr(), B, L, st), "ap_resblock_fwd_gate_save")
+                else:
+                    N.check(lib.ap_resblock_fwd_gate(ctx, n, h_in, film(n), h_out, g, B, L, st), "ap_resblock_fwd_gate")
+        else:
+            def layer(n, g):
+                if pre is not None:
+                    N.check(lib.ap_resblock_fwd_save(ctx, n, N.ptr(hs[n]), film(n), N.ptr(hs[n + 1]), N.ptr(skip), N.ptr(pre[n]),
+                                                     1 if n else 0, B, L, st), "ap_resblock_fwd_save")
+                else:
+                    N.check(lib.ap_resblock_fwd(ctx, n, N.ptr(hs[n]), film(n), N.ptr(hs[n + 1]), N.ptr(skip), 1 if n else 0, B, L, st),
+                            "ap_resblock_fwd")
+        if gimg is None:                                         # the fused block adds its own skip term
+            for n in range(NL):
+                layer(n, None)
+        else:                                                    # one skip GEMM per group of G layers, grouped as ap_eps_fwd groups them
+            self._ensure_gimg(gimg, dev)
+            G = min(plan.group, NL)
+            images = self._gimg[:gimg[0][0]].view(G, B, L, C_)
             for n0 in range(0, NL, G):
                 nl = min(G, NL - n0)
                 for n in range(n0, n0 + nl):
-                    if pre is not None:
-                        N.check(lib.ap_resblock_fwd_gate_save(eng.ctx, n, N.ptr(hs[src(n)]), N.ptr(part[n * C_:(n + 1) * C_]),
-                                                              N.ptr(hs[dst(n)]) if n + 1 < NL else None, gimg[n - n0].data_ptr(),
-                                                              pre[n].data_ptr(), B, L, N.stream()), "ap_resblock_fwd_gate_save")
-                        continue
-                    N.check(lib.ap_resblock_fwd_gate(eng.ctx, n, N.ptr(hs[n]), N.ptr(part[n * C_:(n + 1) * C_]),
-                                                     N.ptr(hs[n + 1]) if n + 1 < NL else None, gimg[n - n0].data_ptr(), B, L, N.stream()),
-                            "ap_resblock_fwd_gate")
-                N.check(lib.ap_skip_gemm(eng.ctx, n0, nl, gimg.data_ptr(), N.ptr(skip), 1 if n0 else 0, B, L, N.stream()), "ap_skip_gemm")
-        for n in range(NL if G == 0 else 0):
-            pt = part[n * C_:(n + 1) * C_]
-            if pre is not None:
-                N.check(lib.ap_resblock_fwd_save(eng.ctx, n, N.ptr(hs[n]), N.ptr(pt), N.ptr(hs[n + 1]), N.ptr(skip), N.ptr(pre[n]),
-                                                 1 if n else 0, B, L, N.stream()), "ap_resblock_fwd_save")
-            else:
-                N.check(lib.ap_resblock_fwd(eng.ctx, n, N.ptr(hs[n]), N.ptr(pt), N.ptr(hs[n + 1]), N.ptr(skip),
-                                            1 if n else 0, B, L, N.stream()), "ap_resblock_fwd")
+                    layer(n, images[n - n0].data_ptr())
+                N.check(lib.ap_skip_gemm(ctx, n0, nl, images.data_ptr(), N.ptr(skip), 1 if n0 else 0, B, L, st), "ap_skip_gemm")
         eps = torch.empty((B, 1, L), device=dev)
-        N.check(lib.ap_final_affine(eng.ctx, N.ptr(skip), None, N.ptr(eps), None, 0.0, 0.0, 0.0, None, 0, 0, 0, B, L,
-                                    N.stream()), "ap_final_affine")
-        return eps, (hs, skip, part, pre)
-
-    def _forward_save_bstore(self, eng, x, step, part):
-        """AP_PREC_BF16_STORE: the sweep ap_eps_fwd runs in this mode (ap_init_conv_u, ap_resblock_fwd_u per layer, one ap_skip_gemm per
-        group: eps equals ap_eps_fwd's bit for bit) with every block also keeping its gate's derivative factors
-        (ap_resblock_fwd_u_save).  The backward is the bf16 mode's (ap_resblock_bwd_bf16_saved): the rounding of the stored residual
-        passes the gradient straight through, everything else about the two forwards is the same arithmetic.  There is no lean
-        form (no fp32 layer inputs exist to recompute from): a link either keeps its factors or is recomputed whole."""
-        lib, dev = eng.lib, x.device
-        B, _, L = x.shape
-        C_, S_, NL = self.C, self.S, self.NL
-        G = self._group(eng)
-        if G <= 0 or not lib.ap_resblock_bwd_bf16_available(eng.ctx, B, L):
-            raise N.NativeError("set_precision('bf16s'): no backward for this shape (res = skip = 256 channels, the deferred-skip form)")
-        hs = torch.empty((1, B, C_, L), device=dev)                         # h_0 in fp32: what ap_init_conv_bwd reads
-        N.check(lib.ap_init_conv(eng.ctx, N.ptr(x), N.ptr(hs[0]), B, L, N.stream()), "ap_init_conv")
-        u = torch.empty((2, B * C_ * L), device=dev, dtype=torch.bfloat16)  # the residual stream's ping-pong pair of u images
-        N.check(lib.ap_init_conv_u(eng.ctx, N.ptr(x), N.ptr(part[:C_]), u[0].data_ptr(), B, L, N.stream()), "ap_init_conv_u")
-        skip = torch.empty((B, S_, L), device=dev)
-        need = min(G, NL) * B * L * C_
-        if self._gimg is None or self._gimg.numel() < need or self._gimg.device != dev:
-            self._gimg = None
-            self._gimg = torch.empty(need, device=dev, dtype=torch.bfloat16)
-        gimg = self._gimg[:need].view(min(G, NL), B, L, C_)
-        fac = torch.empty((NL, int(lib.ap_gate_factor_bytes(B, L))), device=dev, dtype=torch.uint8)
-        for n0 in range(0, NL, G):
-            nl = min(G, NL - n0)
-            for n in range(n0, n0 + nl):
-                last = n + 1 == NL
-                N.check(lib.ap_resblock_fwd_u_save(eng.ctx, n, u[n & 1].data_ptr(), None if last else N.ptr(part[(n + 1) * C_:(n + 2) * C_]),
-                                                   None if last else u[(n + 1) & 1].data_ptr(), gimg[n - n0].data_ptr(), fac[n].data_ptr(),
-                                                   B, L, N.stream()), "ap_resblock_fwd_u_save")
-            N.check(lib.ap_skip_gemm(eng.ctx, n0, nl, gimg.data_ptr(), N.ptr(skip), 1 if n0 else 0, B, L, N.stream()), "ap_skip_gemm")
-        eps = torch.empty((B, 1, L), device=dev)
-        N.check(lib.ap_final_affine(eng.ctx, N.ptr(skip), None, N.ptr(eps), None, 0.0, 0.0, 0.0, None, 0, 0, 0, B, L,
-                                    N.stream()), "ap_final_affine")
-        return eps, (hs, skip, part, fac)
+        N.check(lib.ap_final_affine(ctx, N.ptr(skip), None, N.ptr(eps), None, 0.0, 0.0, 0.0, None, 0, 0, 0, B, L, st), "ap_final_affine")
+        return eps, saved
 
     def backward(self, saved, d_eps: torch.Tensor) -> torch.Tensor:
-        """J_eps(x, t)^T d_eps for the evaluation ``saved`` came from."""
+        """J_eps(x, t)^T d_eps for the evaluation ``saved`` came from; the per-layer form follows what the save holds and the flags
+        as they are now (_backward_form)."""
         eng = self._prepare()
-        lib = eng.lib
-        hs, skip, part, pre = saved
+        lib, ctx = eng.lib, eng.ctx
+        hs, skip, part, pre, fac = saved
         NL, C_, S_ = self.NL, self.C, self.S
         B, L, dev = hs.shape[1], hs.shape[3], hs.device
         d_eps = d_eps.detach().float().contiguous()
@@ -260,64 +299,50 @@ class EpsGrad:
         dskip = r                                                 # reuse
         self._conv(lib, dr, self.wf1_t, None, None, dskip, B, S_, L, S_, 1, 0, 1)
         dh = torch.zeros((B, C_, L), device=dev)                  # the last block's h' output is not used (WaveNet.py:133)
-        if pre is not None and self.net._precision == N.AP_PREC_F32 and lib.ap_resblock_bwd_available(eng.ctx, B, L):
-            # the shipped shape in fp32: two fused launches per layer (ap_resblock_bwd.hip) -- the gate's derivative as the epilogue of
-            # W2^T [dh'; dskip], then the transposed dilated conv in its F(2,3) form with the residual path added in its epilogue
-            dy = torch.empty((B, 2 * C_, L), device=dev)
+        form = _backward_form(self.net._precision, pre is not None, fac is not None, self.fused_bf16,
+                              lib.ap_resblock_bwd_available(ctx, B, L), lib.ap_resblock_bwd_bf16_available(ctx, B, L))
+        if form != "composed":                                    # two fused launches per layer, dh / dh2 ping-pong
+            dy = torch.empty((B, 2 * C_, L), device=dev) if form == "f32" else torch.empty((B, L, 2 * C_), device=dev, dtype=torch.bfloat16)
             dh2 = torch.empty_like(dh)
+            if form == "f32":
+                def layer(n, dh, dh2):
+                    N.check(lib.ap_resblock_bwd(ctx, n, N.ptr(dh), N.ptr(dskip), N.ptr(pre[n]), N.ptr(dy), N.ptr(dh2), B, L, st), "ap_resblock_bwd")
+            elif form == "bf16_saved":                            # dg = W2^T [dh'; dskip], dy = factor . dg, then the transposed dilated conv
+                dsk = torch.empty((B, L, S_), device=dev, dtype=torch.bfloat16)  # dskip once as the bf16 image every layer's kernel stages
+                N.check(lib.ap_bwd_bf16_rows_image(N.ptr(dskip), dsk.data_ptr(), B, S_, L, st), "ap_bwd_bf16_rows_image")
+
+                def layer(n, dh, dh2):
+                    N.check(lib.ap_resblock_bwd_bf16_saved(ctx, n, fac[n].data_ptr(), N.ptr(dh), dsk.data_ptr(), 1, dy.data_ptr(), N.ptr(dh2),
+                                                           B, L, st), "ap_resblock_bwd_bf16_saved")
+            else:                                                 # from the layer INPUTS the forward pass wrote anyway
+                def layer(n, dh, dh2):
+                    N.check(lib.ap_resblock_bwd_bf16(ctx, n, N.ptr(hs[n]), N.ptr(part[n * C_:(n + 1) * C_]), N.ptr(dh), N.ptr(dskip),
+                                                     dy.data_ptr(), N.ptr(dh2), B, L, st), "ap_resblock_bwd_bf16")
             for n in range(NL - 1, -1, -1):
-                N.check(lib.ap_resblock_bwd(eng.ctx, n, N.ptr(dh), N.ptr(dskip), N.ptr(pre[n]), N.ptr(dy), N.ptr(dh2), B, L, st),
-                        "ap_resblock_bwd")
+                layer(n, dh, dh2)
                 dh, dh2 = dh2, dh
-            dx = torch.empty((B, 1, L), device=dev)
-            N.check(lib.ap_init_conv_bwd(N.ptr(hs[0]), N.ptr(self.w0), N.ptr(dh), N.ptr(dx), B, C_, L, st), "ap_init_conv_bwd")
-            return dx
-        if pre is not None and pre.dtype == torch.uint8:
-            # bf16 mode with kept gate factors: dg = W2^T [dh'; dskip], dy = factor . dg, then the transposed dilated conv -- no recomputation
-            dy = torch.empty((B, L, 2 * C_), device=dev, dtype=torch.bfloat16)
-            dh2 = torch.empty_like(dh)
-            dsk = torch.empty((B, L, S_), device=dev, dtype=torch.bfloat16)      # dskip once as the bf16 image every layer's kernel stages
-            N.check(lib.ap_bwd_bf16_rows_image(N.ptr(dskip), dsk.data_ptr(), B, S_, L, st), "ap_bwd_bf16_rows_image")
+        else:
+            z = torch.empty((B, C_ + S_, L), device=dev)         # [RS dh' ; dskip], dskip is the same for every block
+            N.check(lib.ap_copy_channels(N.ptr(dskip), N.ptr(z), B, S_, L, S_, 0, C_ + S_, C_, st), "ap_copy_channels")
+            t1 = torch.empty_like(dh)
+            dg = torch.empty_like(dh)
+            u = torch.empty_like(dh) if pre is None else None
+            a = torch.empty((B, 2 * C_, L), device=dev) if pre is None else None
+            da = torch.empty((B, 2 * C_, L), device=dev)
+            nel = dh.numel()
             for n in range(NL - 1, -1, -1):
-                N.check(lib.ap_resblock_bwd_bf16_saved(eng.ctx, n, pre[n].data_ptr(), N.ptr(dh), dsk.data_ptr(), 1, dy.data_ptr(), N.ptr(dh2), B, L, st),
-                        "ap_resblock_bwd_bf16_saved")
-                dh, dh2 = dh2, dh
-            dx = torch.empty((B, 1, L), device=dev)
-            N.check(lib.ap_init_conv_bwd(N.ptr(hs[0]), N.ptr(self.w0), N.ptr(dh), N.ptr(dx), B, C_, L, st), "ap_init_conv_bwd")
-            return dx
-        if pre is None and self.fused_bf16 and self.net._precision == N.AP_PREC_BF16 and lib.ap_resblock_bwd_bf16_available(eng.ctx, B, L):
-            # bf16 mode at the shipped shape: two launches per layer on the bf16 matrix pipe (ap_resblock_bwd_bf16.hip) from the layer
-            # INPUTS the forward pass wrote anyway -- the dilated conv is recomputed inside the first kernel
-            dy = torch.empty((B, L, 2 * C_), device=dev, dtype=torch.bfloat16)
-            dh2 = torch.empty_like(dh)
-            for n in range(NL - 1, -1, -1):
-                N.check(lib.ap_resblock_bwd_bf16(eng.ctx, n, N.ptr(hs[n]), N.ptr(part[n * C_:(n + 1) * C_]), N.ptr(dh), N.ptr(dskip),
-                                                 dy.data_ptr(), N.ptr(dh2), B, L, st), "ap_resblock_bwd_bf16")
-                dh, dh2 = dh2, dh
-            dx = torch.empty((B, 1, L), device=dev)
-            N.check(lib.ap_init_conv_bwd(N.ptr(hs[0]), N.ptr(self.w0), N.ptr(dh), N.ptr(dx), B, C_, L, st), "ap_init_conv_bwd")
-            return dx
-        z = torch.empty((B, C_ + S_, L), device=dev)             # [RS dh' ; dskip], dskip is the same for every block (the composed path only)
-        N.check(lib.ap_copy_channels(N.ptr(dskip), N.ptr(z), B, S_, L, S_, 0, C_ + S_, C_, st), "ap_copy_channels")
-        t1 = torch.empty_like(dh)
-        dg = torch.empty_like(dh)
-        u = torch.empty_like(dh) if pre is None else None
-        a = torch.empty((B, 2 * C_, L), device=dev) if pre is None else None
-        da = torch.empty((B, 2 * C_, L), device=dev)
-        nel = dh.numel()
-        for n in range(NL - 1, -1, -1):
-            lay = self.layers[n]
-            d = lay["d"]
-            N.check(lib.ap_axpbyc(N.ptr(dh), None, N.ptr(t1), _RS, 0.0, 0.0, nel, st), "ap_axpbyc")
-            N.check(lib.ap_copy_channels(N.ptr(t1), N.ptr(z), B, C_, L, C_, 0, C_ + S_, 0, st), "ap_copy_channels")
-            self._conv(lib, z, lay["g"], None, None, dg, B, C_ + S_, L, C_, 1, 0, 1)
-            if pre is None:                                      # not kept: recompute y = DilConv(h + part_t) + b
-                pt = part[n * C_:(n + 1) * C_]
-                N.check(lib.ap_affine_nchw(N.ptr(hs[n]), N.ptr(self.ones), N.ptr(pt), N.ptr(u), B, C_, L, C_, 0, 0, st),
-                        "ap_affine_nchw")
-                self._conv(lib, u, lay["a"], lay["b1"], None, a, B, C_, L, 2 * C_, 3, d, d)
-            N.check(lib.ap_gate_bwd(N.ptr(a if pre is None else pre[n]), N.ptr(dg), N.ptr(da), B, C_, L, st), "ap_gate_bwd")
-            self._conv(lib, da, lay["u"], None, t1, dh, B, 2 * C_, L, C_, 3, d, d)
+                lay = self.layers[n]
+                d = lay["d"]
+                N.check(lib.ap_axpbyc(N.ptr(dh), None, N.ptr(t1), _RS, 0.0, 0.0, nel, st), "ap_axpbyc")
+                N.check(lib.ap_copy_channels(N.ptr(t1), N.ptr(z), B, C_, L, C_, 0, C_ + S_, 0, st), "ap_copy_channels")
+                self._conv(lib, z, lay["g"], None, None, dg, B, C_ + S_, L, C_, 1, 0, 1)
+                if pre is None:                                      # not kept: recompute y = DilConv(h + part_t) + b
+                    pt = part[n * C_:(n + 1) * C_]
+                    N.check(lib.ap_affine_nchw(N.ptr(hs[n]), N.ptr(self.ones), N.ptr(pt), N.ptr(u), B, C_, L, C_, 0, 0, st),
+                            "ap_affine_nchw")
+                    self._conv(lib, u, lay["a"], lay["b1"], None, a, B, C_, L, 2 * C_, 3, d, d)
+                N.check(lib.ap_gate_bwd(N.ptr(a if pre is None else pre[n]), N.ptr(dg), N.ptr(da), B, C_, L, st), "ap_gate_bwd")
+                self._conv(lib, da, lay["u"], None, t1, dh, B, 2 * C_, L, C_, 3, d, d)
         dx = torch.empty((B, 1, L), device=dev)
         N.check(lib.ap_init_conv_bwd(N.ptr(hs[0]), N.ptr(self.w0), N.ptr(dh), N.ptr(dx), B, C_, L, st), "ap_init_conv_bwd")
         return dx
@@ -367,6 +392,16 @@ def _saved_bytes(saved) -> int:
     return n
 
 
+def _save_level(held, once, full, lean, budget):
+    """What the next link of a chain keeps: ("full", "lean" or None, held', once').  ``held``: bytes the earlier links keep;
+    ``once``: a buffer the first saving link allocates and every later one reuses, so it is charged to that link only."""
+    if held + once + full <= budget:
+        return "full", held + once + full, 0
+    if lean < full and held + once + lean <= budget:
+        return "lean", held + once + lean, 0
+    return None, held, once
+
+
 class _ChainFn(torch.autograd.Function):
     """x_out = chain(x_in): q-sample then the links (step, ca, cb, cs); noise tensors given explicitly.
 
@@ -396,28 +431,20 @@ class _ChainFn(torch.autograd.Function):
                 lean, _ = sizes(cur, False, split=True)
             for (t, ca, cb, cs, draw) in steps:
                 xs.append(cur)
+                saved = None
                 if full is None:                                 # (a gradient object without sizes: measure its first link)
                     eps, saved = grad.forward_save(cur, t)
-                    full = _saved_bytes(saved)
-                    lean = _saved_bytes(saved[:3]) if isinstance(saved, tuple) and len(saved) == 4 else full
-                    if full > budget:
-                        saved = None if lean > budget else saved[:3] + (None,)
-                    if saved is not None:
-                        held += _saved_bytes(saved)
-                    saves.append(saved)
-                elif held + once + full <= budget:
-                    eps, saved = grad.forward_save(cur, t)
-                    held += once + full
-                    once = 0
-                    saves.append(saved)
-                elif lean < full and held + once + lean <= budget:
-                    eps, saved = grad.forward_save(cur, t, acts=False)    # layer inputs only: the backward recomputes the dilated conv
-                    held += once + lean
-                    once = 0
-                    saves.append(saved)
+                    lean_saved = saved.lean() if hasattr(saved, "lean") else saved   # (no lean(): no lean form)
+                    full, lean = _saved_bytes(saved), _saved_bytes(lean_saved)
+                    level, held, once = _save_level(held, once, full, lean, budget)
+                    saved = {"full": saved, "lean": lean_saved, None: None}[level]
                 else:
-                    eps = eps_only(cur, t) if eps_only is not None else grad.forward_save(cur, t)[0]
-                    saves.append(None)
+                    level, held, once = _save_level(held, once, full, lean, budget)
+                    if level is None:
+                        eps = eps_only(cur, t) if eps_only is not None else grad.forward_save(cur, t)[0]
+                    else:                                        # "lean": layer inputs only, the backward recomputes the dilated conv
+                        eps, saved = grad.forward_save(cur, t) if level == "full" else grad.forward_save(cur, t, acts=False)
+                saves.append(saved)
                 nxt = _axpby(cur, eps, ca, cb)
                 if cs != 0.0 and draw:
                     nxt = _axpby(nxt, zs[draw], 1.0, cs)

@@ -365,7 +365,7 @@ def test_bf16_store_eps_vjp_matches_the_bf16_store_oracle_and_the_bf16_mode(dev)
     eg = EpsGrad(net)
     xd, vd = x.to(dev), v.to(dev)
     eps, saved = eg.forward_save(xd, step)
-    assert saved[3].dtype == torch.uint8 and saved[0].shape[0] == 1
+    assert saved.gate_factors.dtype == torch.uint8 and saved.hs.shape[0] == 1
     assert torch.equal(eps, eg.eps_only(xd, step))
     assert eg.saved_bytes(xd, True) == eg.saved_bytes(xd, False)  # no lean form: a link keeps its factors or is recomputed whole
     g = eg.backward(saved, vd).cpu()

@@ -68,7 +68,7 @@ def test_eps_vjp_is_the_same_with_kept_and_with_recomputed_pre_gate_activations(
     eg = G.EpsGrad(net)
     eps_a, saved_a = eg.forward_save(x, step)
     eps_b, saved_b = eg.forward_save(x, step, acts=False)
-    assert saved_a[3] is not None and saved_a[3].shape == (3, B, 512, L) and saved_b[3] is None
+    assert saved_a.pre_gate is not None and saved_a.pre_gate.shape == (3, B, 512, L) and saved_b.pre_gate is None
     # (kept activations: the direct-form block with the pre-gate store; lean: the F(2,3) block -- the same eps to fp32 rounding)
     assert rel_err(eps_a.cpu().numpy(), eps_b.cpu().numpy()) < 2e-6
     ga, gb = eg.backward(saved_a, v), eg.backward(saved_b, v)
@@ -80,7 +80,7 @@ def test_eps_vjp_is_the_same_with_kept_and_with_recomputed_pre_gate_activations(
     grads = []
     old = G.SAVE_BUDGET_BYTES
     try:
-        for budget in (old, full + 2 * G._saved_bytes(saved_a[:3]) + 1, 1):
+        for budget in (old, full + 2 * G._saved_bytes(saved_a.lean()) + 1, 1):
             G.SAVE_BUDGET_BYTES = budget
             xg = x.clone().requires_grad_(True)
             out = G.differentiable_chain(net, xg, steps, 0.9, 0.1, zs)
@@ -583,12 +583,12 @@ def test_bf16_eps_vjp_runs_on_the_bf16_backward_and_matches_the_bf16_oracle(dev)
     # round 6: by default the forward pass keeps the gate's derivative factors (an opaque uint8 image per layer) and only the
     # first layer's input; the backward reads them instead of recomputing the dilated conv
     eps, saved = eg.forward_save(xd, step)
-    assert saved[3] is not None and saved[3].dtype == torch.uint8 and saved[0].shape[0] == 3
+    assert saved.gate_factors is not None and saved.gate_factors.dtype == torch.uint8 and saved.hs.shape[0] == 3
     assert torch.equal(eps, eg.eps_only(xd, step))               # the saving forward runs the chain's own deferred-skip form: same eps, bit for bit
     g_kept = eg.backward(saved, vd).cpu()
     eg.keep_gate_factors = False                                 # the round-5 form: every layer's input kept, the dilated conv recomputed
     eps2, saved2 = eg.forward_save(xd, step)
-    assert saved2[3] is None and torch.equal(eps2, eps)
+    assert saved2.pre_gate is None and saved2.gate_factors is None and torch.equal(eps2, eps)
     g = eg.backward(saved2, vd).cpu()
     eg.fused_bf16 = False
     g_fp32 = eg.backward(saved2, vd).cpu()                       # same layer inputs, fp32 GEMMs

@@ -712,6 +712,27 @@ def test_saved_bytes_estimate_equals_what_forward_save_keeps(dev, mode, acts, ke
         del saved
 
 
+@pytest.mark.parametrize("C_,mode,acts,keep", [(64, "f32", True, True), (64, "f32", False, True), (256, "f32", True, True),
+                                               (256, "f32", False, True), (256, "f32s", True, True), (256, "bf16", True, True),
+                                               (256, "bf16", True, False), (256, "bf16s", True, True)])
+def test_saved_bytes_is_exactly_what_forward_save_keeps(dev, C_, mode, acts, keep):
+    """saved_bytes sums the list forward_save allocates from (_grad._link_buffers): the link's bytes and the one-off gate-image
+    buffer's agree to the byte, not to 1 %."""
+    from audiopure_amd.diffusion_models import _grad as G
+    from audiopure_amd.diffusion_models.DiffWave_Unconditional.WaveNet import WaveNet_Speech_Commands
+    cfg = synth.mini_wavenet_config(C_, 12, 12)
+    net = WaveNet_Speech_Commands(**cfg)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.wavenet_state_dict(cfg, SEED).items()}, strict=True)
+    eg = G.EpsGrad(net.to(dev).set_precision(mode))
+    eg.keep_gate_factors = keep
+    x = torch.from_numpy(synth.waveforms(2, 1500, seed=4)).to(dev)
+    per_link, once = eg.saved_bytes(x, acts, split=True)
+    _, saved = eg.forward_save(x, 2.0, acts)
+    assert per_link == G._saved_bytes(saved), (per_link, G._saved_bytes(saved))
+    assert once == (eg._gimg.numel() * eg._gimg.element_size() if eg._gimg is not None else 0)
+    assert eg.saved_bytes(x, acts, split=True) == (per_link, 0)   # (warm: the buffer is there)
+
+
 def test_chain_keeps_exactly_the_links_the_budget_holds(dev):
     """A 5-link bf16 chain under SAVE_BUDGET_BYTES = the one-off gate-image buffer + 2 x one link's true bytes + a margin: exactly two
     links keep their saves, and what they keep plus that buffer stays within the budget (restored in a finally, as in
