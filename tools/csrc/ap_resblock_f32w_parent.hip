@@ -1,3 +1,10 @@
+// TOOLS ONLY (never in the product library): the F(2,3) fp32 block as it stood before the GEMM1 diet of ap_resblock_f32w.hip (carried
+// weight prefetch, no X request past the last chunk, launch constants in LDS) -- the kernel and its launch kept verbatim under other names, reading the
+// same packed images of the context.  tests/test_gpu_f32w_diet.py holds the product kernel to it bit for bit, tools/ab_f32w.py times
+// against it.  h_out NULL = the last layer's form, pre_gate non-NULL = the SAVE form.
+// A baseline, not a second implementation: delete it, with that test and the diet section of the tool, at the first change to
+// ap_resblock_f32w.hip that is meant to alter results or that needs another baseline.
+//
 // AP_PREC_F32, shipped shape (res = skip = 256 channels): fused Residual_block.forward (WaveNet.py:75-97) with the dilated k = 3
 // conv (WaveNet.py:87) in F(2,3) minimal-filtering form over the dilation pair.
 //
@@ -26,8 +33,6 @@
 // (one adder per element per launch: deterministic).
 #include "ap_common.h"
 
-#include <type_traits>
-
 namespace ap {
 
 namespace {
@@ -45,64 +50,11 @@ constexpr int POFF_ = GOFF_ + 64 * GS_;         // Q16: output patches, [wave 4]
 constexpr int PS_ = 36;
 constexpr int LDS_FLOATS_ = GOFF_ + 64 * GS_;   // 103,424 B
 constexpr int LDS_FLOATS_Q16_ = POFF_ + 4 * 2 * 32 * PS_;   // 140,288 B
-constexpr int NCONST_ = 5 * WC_;           // b1 (2C) | b2 (2C) | part_t (C): the launch constants' LDS copy (5 KB)
-// What the kernel leaves out that the result never needed (bits of the DIET template argument; tools builds instantiate each alone
-// for tools/ab_f32w.py, the product both -- profiles/f32w_diet_ab.txt has the A/B.  A third item, a four-deep X ring with one
-// barrier per chunk pair, measured null there and is not in this source):
-constexpr int DIET_CARRY_ = 2;           // the last k-group's wrapped weight loads ARE the next tile's first units; no X request past chunk 7
-constexpr int DIET_CONST_ = 4;           // b1, b2, part_t copied to LDS once per launch: the accumulator inits read LDS, not memory
-#ifndef AP_F32W_DIET
-#define AP_F32W_DIET 6
-#endif
-// the 4-byte epilogue form (ragged clip lengths) holds 64 residual values across GEMM2 and has no registers to spare: no item
-constexpr int DIET4_ = 0;
 constexpr unsigned UNIT_BYTES_ = 4 * 64 * 16;   // one (k-group, product) unit of a wave's GEMM1 image: 4 row tiles x 64 lanes x 16 B
 constexpr unsigned W1W_WAVE_BYTES_ = NCH_ * 4 * 4 * UNIT_BYTES_;   // 512 KB per wave and layer
 constexpr unsigned W2W_WAVE_BYTES_ = (WC_ / 8) * UNIT_BYTES_;      // 128 KB per wave and layer
 
 }  // namespace
-
-// GEMM1 image: [wave 4][chunk 8][k-group 4][product 4][row tile 4][lane 64][4]; lane (i, hh), element e = k-step e of the group:
-// channel 32 chunk + 8 kg + 4 hh + e (the k a lane's ds_read_b128 B fragment holds for that step); row tiles interleave the tanh
-// (even) and sigmoid (odd) halves as in pack_w1_kernel.
-__global__ void pack_w1w_kernel(const float *__restrict__ w1f, float *__restrict__ out) {
-  constexpr int C = WC_;
-  const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= 4u * NCH_ * 4 * 4 * 4 * 64 * 4) return;
-  const int e = idx & 3, lane = (idx >> 2) & 63, rt = (idx >> 8) & 3, comp = (idx >> 10) & 3, kg = (idx >> 12) & 3,
-            ch = (idx >> 14) & 7, w = idx >> 17;
-  const int i = lane & 31, hh = lane >> 5;
-  const int c = 32 * ch + 8 * kg + 4 * hh + e;
-  const int o = (rt & 1) * C + 64 * w + 32 * (rt >> 1) + i;
-  const float *p = w1f + ((size_t)o * C + c) * 3;
-  const double w0 = p[0], w1 = p[1], w2 = p[2];
-  const double v = comp == 0 ? w0 : comp == 1 ? (w0 + w1 + w2) * 0.5 : comp == 2 ? (w0 - w1 + w2) * 0.5 : w2;
-  out[idx] = (float)v;
-}
-
-// GEMM2 image: [wave 4][k-group 32][row tile 4][lane 64][4]; channel 8 kg + 4 hh + e; row tiles 0,1 = res_conv rows of the wave's
-// 64 channels, 2,3 = skip_conv rows of the same channels (w2f = [res rows; skip rows]).
-__global__ void pack_w2w_kernel(const float *__restrict__ w2f, float *__restrict__ out) {
-  constexpr int C = WC_;
-  const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= 4u * (C / 8) * 4 * 64 * 4) return;
-  const int e = idx & 3, lane = (idx >> 2) & 63, rt = (idx >> 8) & 3, kg = (idx >> 10) & 31, w = idx >> 15;
-  const int i = lane & 31, hh = lane >> 5;
-  const int c = 8 * kg + 4 * hh + e;
-  const int o = (rt >> 1) * C + 64 * w + 32 * (rt & 1) + i;
-  out[idx] = w2f[(size_t)o * C + c];
-}
-
-int launch_pack_f32w(ap_ctx *ctx, hipStream_t st) {
-  const int C = ctx->C, S = ctx->S;
-  const size_t n1f = (size_t)2 * C * C * 3, n2 = (size_t)(C + S) * C, n1w = (size_t)4 * 2 * C * C;
-  for (int n = 0; n < ctx->NL; n++) {
-    pack_w1w_kernel<<<(unsigned)((n1w + 255) / 256), 256, 0, st>>>(ctx->w1f + n * n1f, ctx->w1w + n * n1w);
-    pack_w2w_kernel<<<(unsigned)((n2 + 255) / 256), 256, 0, st>>>(ctx->w2f + n * n2, ctx->w2w + n * n2);
-  }
-  AP_HIP(hipGetLastError());
-  return 0;
-}
 
 // SAVE (the differentiable path's forward pass, ap_resblock_fwd_save): the pre-gate activations y = DilConv(u) + b are also written
 // to aout [B][2C][L] (rows 0..C-1 the tanh half, C..2C-1 the sigmoid half: what ap_resblock_bwd reads).
@@ -111,16 +63,13 @@ int launch_pack_f32w(ap_ctx *ctx, hipStream_t st) {
 // rows as 16-byte loads (skip += as a read-modify-write: one workgroup owns a tile within a launch, launches are stream-ordered,
 // so the sum is as deterministic as the float atomics of the 4-byte form).  A CU's store path moves a 4-byte-per-lane store
 // stream at a fraction of its 16-byte rate: the 4-byte epilogue cost 6.5 % of the launch (tools/ab_f32w.py).
-template <bool NOH, bool SAVE = false, bool Q16 = false, int DIET = AP_F32W_DIET>
-__global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
+template <bool NOH, bool SAVE = false, bool Q16 = false>
+__global__ __launch_bounds__(256, 1) void resblock_f32w_parent_kernel(
     const float *__restrict__ hin, const float *__restrict__ pt, float *__restrict__ hout, float *__restrict__ skip,
     const float *__restrict__ w1w, const float *__restrict__ b1, const float *__restrict__ w2w,
     const float *__restrict__ b2, int L, int logd, int accumulate, int ntiles, int nblk, float *__restrict__ aout) {
   constexpr int C = WC_;
-  constexpr bool CARRY = (DIET & DIET_CARRY_) != 0, CONST = (DIET & DIET_CONST_) != 0;
-  // LDS map (floats): X sub-buffers 0, 1 | g image | Q16: output patches | CONST: b1, b2, part_t
-  constexpr int COFF_ = Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_;
-  __shared__ __attribute__((aligned(16))) float lds[COFF_ + (CONST ? NCONST_ : 0)];
+  __shared__ __attribute__((aligned(16))) float lds[Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -147,10 +96,6 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     }
   }
   if (t_first >= t_end) return;
-  if constexpr (CONST) {                                         // (a whole workgroup leaves above or none does: the barrier is uniform)
-    for (int i = tid; i < NCONST_; i += 256) lds[COFF_ + i] = i < 2 * C ? b1[i] : i < 4 * C ? b2[i - 2 * C] : pt[i - 4 * C];
-    __syncthreads();
-  }
 
   auto uni_rsrc = [&](const void *base, unsigned bytes) {
     const uint64_t hb = (uint64_t)base;
@@ -168,11 +113,6 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   auto ld4 = [&](const __amdgpu_buffer_rsrc_t &rs, int idx) {    // four consecutive floats at element idx (16-byte aligned)
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)idx * 4u, 0, 0));
   };
-  // the launch constants for the accumulator inits.  CONST: from their LDS copy -- as buffer loads they queue behind the previous
-  // tile's skip stores (vmcnt retires in order) at every tile's top and again before GEMM2
-  auto ld_b1 = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + idx); else return ld4(b1rs, idx); };
-  auto ld_b2 = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + 2 * C + idx); else return ld4(b2rs, idx); };
-  auto ld_pt = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + 4 * C + idx); else return ld4(ptrs, idx); };
 
   auto load_a1 = [&](f32x4(&a)[4], unsigned unit) {             // one (k-group, product) unit of GEMM1 weights: 4 row tiles
 #pragma unroll
@@ -257,7 +197,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
       const int obase = (rt & 1) * C + 64 * wave + 32 * (rt >> 1);
 #pragma unroll
       for (int q = 0; q < 4; q++) {
-        const f32x4 bv = ld_b1(obase + 8 * q + 4 * hh);
+        const f32x4 bv = ld4(b1rs, obase + 8 * q + 4 * hh);
         acc[1][rt][4 * q + 0] = bv[0];
         acc[1][rt][4 * q + 1] = bv[1];
         acc[1][rt][4 * q + 2] = bv[2];
@@ -269,15 +209,12 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     store_x(lds);
     __syncthreads();
 
-    // ---- GEMM1: 8 chunks x 4 k-groups x 4 products; a unit = 16 MFMAs on one B fragment.  Chunk c + 1 is requested at chunk c's top and
-    // staged in its unit 12.  Without CARRY every chunk does so (no branches: the last one re-requests itself, unused); with it the
-    // last chunk runs a body that requests and stages nothing.
-    constexpr int NSTAGE = CARRY ? NCH_ - 1 : NCH_;
+    // ---- GEMM1: 8 chunks x 4 k-groups x 4 products; a unit = 16 MFMAs on one B fragment
     const float *xfrag = lds + j * XS_ + 4 * hh;
-    auto chunk = [&](int ch, auto stage_tag) __attribute__((always_inline)) {
-      constexpr bool STAGE = decltype(stage_tag)::value;
+#pragma unroll 1
+    for (int ch = 0; ch < NCH_; ch++) {
       const float *xb = xfrag + (ch & 1) * XBUF_;
-      if constexpr (STAGE) issue_x(ch + 1 < NCH_ ? ch + 1 : ch);
+      issue_x(ch + 1 < NCH_ ? ch + 1 : ch);   // (no branches in this loop: the last chunk re-requests itself, unused)
       f32x4 bq[2];
       bq[0] = *reinterpret_cast<const f32x4 *>(xb);
       __builtin_amdgcn_sched_barrier(0);
@@ -289,13 +226,13 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
           if (u + 1 < 16) bq[(u + 1) & 1] = *reinterpret_cast<const f32x4 *>(xb + ((u + 1) & 3) * XCOMP_ + ((u + 1) >> 2) * 8);
           // the next chunk's FiLM add / padding / differences / LDS writes ride in the MFMA gaps of unit 12 (the X loads were
           // requested twelve units = 12 k cycles ago)
-          if (STAGE && u == 12) store_x(lds + ((ch + 1) & 1) * XBUF_);
+          if (u == 12) store_x(lds + ((ch + 1) & 1) * XBUF_);
 #pragma unroll
           for (int e = 0; e < 4; e++)
 #pragma unroll
             for (int rt = 0; rt < 4; rt++)
               acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], acc[comp][rt], 0, 0, 0);
-          if (STAGE && u == 12) {
+          if (u == 12) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -304,21 +241,11 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
             __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
           }
           __builtin_amdgcn_sched_barrier(0);
-          // the same product's unit of the next k-group takes over this unit's registers (the last k-group wraps to the image's
-          // first units: CARRY keeps them for the next tile -- same layer, same image; otherwise unused)
-          load_a1(a[comp], (unsigned)((16 * ch + u + 4) & (16 * NCH_ - 1)));
+          // the same product's unit of the next k-group takes over this unit's registers
+          load_a1(a[comp], (unsigned)((16 * ch + u + 4) & (16 * NCH_ - 1)));   // (the last k-group wraps to the image's first units, unused)
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-    };
-#pragma unroll 1
-    for (int ch = 0; ch < NSTAGE; ch++) {
-      chunk(ch, std::true_type{});
-      __syncthreads();
-    }
-#pragma unroll 1
-    for (int ch = NSTAGE; ch < NCH_; ch++) {
-      chunk(ch, std::false_type{});
       __syncthreads();
     }
 
@@ -385,8 +312,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           const int c = cb + 8 * q + 4 * hh;
-          f32x4 bv = ld_b2((rt < 2 ? 0 : C) + c);
-          if (rt < 2) bv += ld_pt(c);                            // u = h + part_t re-enters the residual (WaveNet.py:84,97)
+          f32x4 bv = ld4(b2rs, (rt < 2 ? 0 : C) + c);
+          if (rt < 2) bv += ld4(ptrs, c);                        // u = h + part_t re-enters the residual (WaveNet.py:84,97)
 #pragma unroll
           for (int ct = 0; ct < 2; ct++) {
             acc2[rt][ct][4 * q + 0] = bv[0];
@@ -505,10 +432,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
       }
       {
         set_tile(tile + t_step < t_end ? tile + t_step : tile);  // (the last tile re-requests itself, unused)
-        if constexpr (!CARRY) {
 #pragma unroll
-          for (int u = 0; u < 4; u++) load_a1(a[u], (unsigned)u);
-        }
+        for (int u = 0; u < 4; u++) load_a1(a[u], (unsigned)u);
         issue_x(0);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -530,10 +455,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     // lets the youngest 63 operations -- the atomics -- stay outstanding)
     {
       set_tile(tile + t_step < t_end ? tile + t_step : tile);    // (the last tile re-requests itself, unused)
-      if constexpr (!CARRY) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) load_a1(a[u], (unsigned)u);
-      }
+      for (int u = 0; u < 4; u++) load_a1(a[u], (unsigned)u);
       issue_x(0);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -574,21 +497,10 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   }
 }
 
-#ifdef AP_TOOLS
-static int g_no_q16 = 0;                                        // ap_debug_f32w_q16(0): the 4-byte epilogue for every clip length (A/B)
-static int g_diet = AP_F32W_DIET;                               // ap_debug_f32w_diet(mask): the h'-writing Q16 block with another DIET mask (A/B)
-#else
 static constexpr int g_no_q16 = 0;
-#endif
-
-bool resblock_f32w_serves(const ap_ctx *ctx, int B, int L) {
-  if (ctx->cfg.precision != AP_PREC_F32 || ctx->f32_form != 1 || ctx->C != WC_ || ctx->S != WC_ || !ctx->w1w) return false;
-  if ((size_t)2 * WC_ * (size_t)L * 4 >= ((size_t)1 << 31)) return false;   // (the pre-gate rows of the SAVE form: 2C rows per clip)
-  return (long long)B * ((L + 2 * NP_ - 1) / (2 * NP_) + 1) < (1ll << 31);
-}
 
 // returns 1 if the shape is not served (caller: the direct-form kernel)
-int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
+int launch_resblock_f32w_parent(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
                          int B, int L, hipStream_t st, float *aout) {
   if (!resblock_f32w_serves(ctx, B, L)) return 1;
   const int g_ncu = device_cu_count();
@@ -607,48 +519,22 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
   const bool q16 = (L & 3) == 0 && !g_no_q16;
   if (aout) {
     if (!hout) { set_error("resblock (save): needs an h' buffer"); return -22; }
-    if (q16) resblock_f32w_kernel<false, true, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
-    else resblock_f32w_kernel<false, true, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
+    if (q16) resblock_f32w_parent_kernel<false, true, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
+    else resblock_f32w_parent_kernel<false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
     AP_HIP(hipGetLastError());
     return 0;
   }
-#ifdef AP_TOOLS
-#define AP_F32W_AB(M)                                                                                                             \
-  if (hout && q16 && g_diet == M) {                                                                                               \
-    resblock_f32w_kernel<false, false, true, M><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, \
-                                                                      ntiles, (int)nblk, nullptr);                                \
-    AP_HIP(hipGetLastError());                                                                                                    \
-    return 0;                                                                                                                     \
-  }
-  if (g_diet != AP_F32W_DIET) { AP_F32W_AB(0) AP_F32W_AB(2) AP_F32W_AB(4) }
-#undef AP_F32W_AB
-#endif
-  if (hout && q16) resblock_f32w_kernel<false, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
-  else if (hout) resblock_f32w_kernel<false, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
-  else if (q16) resblock_f32w_kernel<true, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
-  else resblock_f32w_kernel<true, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  if (hout && q16) resblock_f32w_parent_kernel<false, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  else if (hout) resblock_f32w_parent_kernel<false><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  else if (q16) resblock_f32w_parent_kernel<true, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  else resblock_f32w_parent_kernel<true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
   AP_HIP(hipGetLastError());
   return 0;
 }
 
 }  // namespace ap
 
-#ifdef AP_TOOLS
-extern "C" int ap_debug_f32w_q16(int on) {
-  ap::g_no_q16 = on ? 0 : 1;
-  return 0;
+extern "C" int ap_debug_resblock_f32w_parent(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out, float *skip,
+                                             int accumulate, int B, int L, void *stream, float *pre_gate) {
+  return ap::launch_resblock_f32w_parent(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
 }
-// the block's launch as the chains call it: h_out NULL = the last layer's form (no per-block entry point of include/audiopure.h reaches
-// it), pre_gate non-NULL = the SAVE form
-extern "C" int ap_debug_resblock_f32w(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out, float *skip,
-                                      int accumulate, int B, int L, void *stream, float *pre_gate) {
-  return ap::launch_resblock_f32w(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
-}
-// the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with DIET mask 0, 2, 4 or 6; every other form keeps
-// the product's mask
-extern "C" int ap_debug_f32w_diet(int mask) {
-  if (mask != 0 && mask != 2 && mask != 4 && mask != 6) return -22;
-  ap::g_diet = mask;
-  return 0;
-}
-#endif
