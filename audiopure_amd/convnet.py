@@ -191,8 +191,15 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
             stride = _pair(args[2]) if len(args) > 2 and args[2] else k
             pad = _pair(args[3]) if len(args) > 3 else (0, 0)
             _need(k[0] == k[1] and stride[0] == stride[1] and pad[0] == pad[1], "shape / argument pattern not lowered")
-            if op == "avg_pool2d":
+            # ap_pool2d computes the floor shape of an undilated window: what it cannot run is refused, never traced at torch's shape
+            if op == "avg_pool2d":        # (self, kernel_size, stride, padding, ceil_mode, count_include_pad, divisor_override)
+                _need(not (len(args) > 4 and args[4]) and not kwargs.get("ceil_mode", False), "pooling with ceil_mode=True not lowered")
                 _need(pad[0] == 0 or (len(args) <= 5 or args[5]), "count_include_pad=False not lowered")
+                _need(len(args) <= 6 or args[6] is None, "avg_pool2d with divisor_override not lowered")
+            else:                         # (self, kernel_size, stride, padding, dilation, ceil_mode)
+                dil = _pair(args[4]) if len(args) > 4 else _pair(kwargs.get("dilation", 1))
+                _need(tuple(dil) == (1, 1), "dilated max_pool2d not lowered")
+                _need(not (len(args) > 5 and args[5]) and not kwargs.get("ceil_mode", False), "pooling with ceil_mode=True not lowered")
             v = get(xin)
             if not v.full:
                 c = plan.new_buf(v.C, v.H, v.W)
@@ -548,8 +555,10 @@ class NativeConvNet(nn.Module):
         torch.cuda.synchronize(dev)
         self._bwd_packed = packs
 
-    def _input_grad(self, bufs, dout):
-        """Reverse sweep over the plan: every step adds its contribution into the gradient buffers of its inputs."""
+    def _input_grad(self, bufs, dout, keep=None):
+        """Reverse sweep over the plan: every step adds its contribution into the gradient buffers of its inputs.
+        ``keep``: a dict that receives every gradient buffer of the sweep ({buf id: [B, C, H, W]}, the layout of ``bufs``) -- for
+        tests that check the sweep step by step; the arithmetic does not depend on it."""
         if getattr(self, "_bwd_packed", None) is None or self._bwd_key is not self._dev_weights:
             self._prepare_backward()
             self._bwd_key = self._dev_weights
@@ -625,7 +634,10 @@ class NativeConvNet(nn.Module):
                 N.check(lib.ap_pool2d_bwd(N.ptr(bufs[v.buf]), N.ptr(gbuf(o.buf)), N.ptr(tmp), B * v.C, v.H, v.W, p["k"], p["stride"],
                                           p["pad"], int(p["is_max"]), st_), "ap_pool2d_bwd")
                 acc(tmp, v.C, v.H * v.W, v.C, 0, v)
-        return gbuf(plan.input.buf)
+        dx = gbuf(plan.input.buf)
+        if keep is not None:
+            keep.update(grads)
+        return dx
 
     def _zeros(self, n, dev):
         z = getattr(self, "_zero_vec", None)

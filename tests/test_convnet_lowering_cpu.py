@@ -91,6 +91,56 @@ def test_unsupported_graph_is_loud():
         lower(Bad())
 
 
+def test_pooling_arguments_the_pool_kernel_does_not_implement_are_refused():
+    """ap_pool2d computes the floor output shape of an undilated window.  ceil_mode=True and a dilated max-pool used to be traced
+    at torch's shape and run with the kernel's arithmetic -- a wrong answer without an error; they are refused like every other
+    pattern without a kernel.  The default arguments still lower, and replay to the module's output."""
+    def net(pool):
+        return nn.Sequential(nn.Conv2d(1, 4, 3, padding=1), nn.ReLU(), pool, nn.Conv2d(4, 4, 3, padding=1), nn.AdaptiveAvgPool2d(1),
+                             nn.Flatten(), nn.Linear(4, 3))
+    for pool in (nn.MaxPool2d(2, 2, ceil_mode=True), nn.MaxPool2d(3, 2, 1, ceil_mode=True), nn.AvgPool2d(2, 2, ceil_mode=True),
+                 nn.MaxPool2d(3, 1, 1, dilation=2), nn.MaxPool2d(2, 2, dilation=(1, 2))):
+        with pytest.raises(NotImplementedError, match="convnet lowering"):
+            lower(net(pool), (1, 9, 9))
+    x = torch.from_numpy(synth.uniform("pool/x", (2, 1, 10, 10), 1, -2.0, 2.0))
+    for pool in (nn.MaxPool2d(2, 2), nn.MaxPool2d(3, 2, 1), nn.AvgPool2d(2, 2), nn.MaxPool2d(2, 2, 0, 1, False, False),
+                 nn.AvgPool2d(2, 2, 0, False, True)):
+        m = synth_init(net(pool), 4).eval()
+        plan = lower(m, (1, 10, 10))
+        assert [st.kind for st in plan.steps].count("pool") == 2
+        with torch.no_grad():
+            assert float((run_plan_torch(plan, x) - m(x)).abs().max()) < 1e-5
+
+
+def test_linearised_replay_is_the_modules_input_gradient():
+    """oracle.convnet_plan_oracle.replay_linearised (the reference of tests/test_gpu_convnet_steps.py) checked without a GPU: with
+    the ReLU masks and max-pool positions of a float32 pass over the plan, its float64 input gradient is torch autograd through
+    the module -- through the float64 module to the float32-vs-float64 figure itself, through the float32 module (whose own
+    arithmetic has that error) to the tolerance derived from it.  The three step-test networks at all three shapes, the
+    remainder-0 strided convolutions and floor poolings of 33 x 47 included."""
+    import copy
+    from conftest import rel_err
+    from oracle.convnet_plan_oracle import forward_bufs_torch, read_val, replay_gradients
+    from test_gpu_convnet_steps import GRAD_SHAPES, GRAD_TOL, REPLAY_F32_ERR, STEP_NETS, step_case
+    for name in STEP_NETS:
+        for chw in GRAD_SHAPES:
+            m, x, dout = step_case(name, chw)
+            plan = lower(m, chw)
+            bufs = forward_bufs_torch(plan, x)                              # float32, every buffer kept
+            assert torch.equal(read_val(bufs, plan.output).reshape(dout.shape), run_plan_torch(plan, x))
+            dx64, g64 = replay_gradients(plan, bufs, dout, torch.float64)
+            assert len(g64) == len(plan.steps) and all(g is not None for g in g64)
+            dx32, g32 = replay_gradients(plan, bufs, dout, torch.float32)
+            fig = max([rel_err(dx32.numpy(), dx64.numpy())] + [rel_err(a.numpy(), b.numpy()) for a, b in zip(g32, g64)])
+            assert fig < GRAD_TOL, (name, chw, fig)                         # (the figure GRAD_TOL was derived from: 4 x its worst)
+            xd = x.double().requires_grad_(True)
+            (gd,) = torch.autograd.grad(copy.deepcopy(m).double()(xd), xd, dout.double())
+            assert rel_err(dx64.numpy(), gd.numpy()) < REPLAY_F32_ERR, (name, chw, rel_err(dx64.numpy(), gd.numpy()))
+            xf = x.clone().requires_grad_(True)
+            (gf,) = torch.autograd.grad(m(xf), xf, dout)
+            assert rel_err(dx64.numpy(), gf.numpy()) < GRAD_TOL, (name, chw, rel_err(dx64.numpy(), gf.numpy()))
+
+
 def test_restated_models_have_reference_state_dict_keys():
     import os
     g = np.load(os.path.join(os.path.dirname(__file__), "golden", "golden_convnets_v1.npz"))
