@@ -99,7 +99,7 @@ extern "C" int ap_ctx_create(const ap_config *cfg, ap_ctx **out) {
   c->loaded = false;
   c->slab = nullptr;
   c->slab_bf = nullptr;
-  c->w1p_bf = c->w2p_bf = c->wf1p_bf = c->w1q_bf = nullptr;
+  c->w1p_bf = c->w2p_bf = c->wf1p_bf = nullptr;
   c->slab_s = nullptr;
   c->slab_w = nullptr;
   c->w1w = c->w2w = nullptr;
@@ -292,17 +292,10 @@ extern "C" int ap_ctx_load_wavenet(ap_ctx *ctx, const float *blob_dev, size_t n_
   if (c.precision == AP_PREC_BF16 || c.precision == AP_PREC_BF16_STORE) {
     const size_t n1 = NL * 2 * C * C * 3, n2 = NL * (C + S) * C;
     if (!ctx->slab_bf) {
-#ifdef AP_TOOLS                                                   // + the 16x16x32 GEMM1 image of the tools library's M16 instantiation
-      AP_HIP(hipMalloc(&ctx->slab_bf, (n1 + n2 + (size_t)S * S + n1) * 2));
-#else
       AP_HIP(hipMalloc(&ctx->slab_bf, (n1 + n2 + (size_t)S * S) * 2));
-#endif
       ctx->w1p_bf = ctx->slab_bf;
       ctx->w2p_bf = (char *)ctx->slab_bf + n1 * 2;
       ctx->wf1p_bf = (char *)ctx->slab_bf + (n1 + n2) * 2;     // final conv's first 1x1 (bf16 A-operand image)
-#ifdef AP_TOOLS
-      ctx->w1q_bf = (char *)ctx->slab_bf + (n1 + n2 + (size_t)S * S) * 2;   // GEMM1 image for the 16x16x32 MFMA shape
-#endif
     }
     rc = launch_pack_bf16(ctx, st);
     if (rc) return rc;
@@ -374,14 +367,9 @@ extern "C" int ap_ctx_get_folded(ap_ctx *ctx, int which, int layer, float *out_d
 //            | AP_PREC_BF16 with a skip group G > 0: g images [G][B][L][C] bf16 (the deferred-skip form: ap_skipgemm_bf16.hip)
 // AP_PREC_BF16_STORE: h_a, h_b are the bf16 u images [B][C/32][L][32] (half the bytes); always the deferred-skip form (G = 0 means
 //            one group of all layers)
-//            | tools builds, AP_PREC_BF16: ub_a, ub_b [B][C/32][L][32] bf16 (the operand-image experiment: ap_resblock_bf16p.hip, UB)
-#ifdef AP_TOOLS
-namespace ap { extern int g_dbg_bf16; }
-#endif
 namespace {
 struct Ws {
   float *ha, *hb, *skip, *xa, *xb, *pt;
-  void *uba, *ubb;
   char *gimg;          // [G][B][L][C] bf16, or null
   size_t gslot;        // bytes per slot
   size_t bytes;
@@ -403,7 +391,6 @@ Ws carve(const ap_ctx *ctx, void *base, int B, int L) {
   w.xa = p; p += xl;
   w.xb = p; p += xl;
   w.pt = p; p += pt;
-  w.uba = w.ubb = nullptr;
   w.gimg = nullptr;
   w.gslot = 0;
   if (skip_group_of(ctx) > 0) {
@@ -411,13 +398,6 @@ Ws carve(const ap_ctx *ctx, void *base, int B, int L) {
     w.gimg = (char *)p;
     p += al(((size_t)skip_group_of(ctx) * w.gslot + 3) / 4);
   }
-#ifdef AP_TOOLS
-  if (ctx->cfg.precision == AP_PREC_BF16) {
-    const size_t ub = al(((size_t)B * ctx->C * L + 1) / 2);
-    w.uba = p; p += ub;
-    w.ubb = p; p += ub;
-  }
-#endif
   w.bytes = (size_t)((char *)p - (char *)base);
   return w;
 }
@@ -479,24 +459,6 @@ int run_net(ap_ctx *ctx, const float *x, float step, const Ws &w, int B, int L, 
   rc = launch_init_conv(ctx, x, w.ha, B, L, st);
   if (rc) return rc;
   float *hin = w.ha, *hout = w.hb;
-#ifdef AP_TOOLS
-  // tools bit 0x400000 (tools/ab_bf16_ub.py): each layer hands the next one its bf16 operand image -- bit-identical, 3 % slower
-  // (the block runs at the board's power cap; the image's extra stores cost more than its staging saves: DESIGN.md 3.4)
-  if (w.uba != nullptr && (ap::g_dbg_bf16 & 0x400000)) {
-    rc = launch_make_ub(w.ha, w.pt, w.uba, B, ctx->C, L, st);
-    if (rc) return rc;
-    void *uin = w.uba, *uout = w.ubb;
-    for (int n = 0; n < ctx->NL; n++) {
-      const bool last = n + 1 == ctx->NL;
-      const UbArgs ub = {uin, last ? nullptr : uout, w.pt + (size_t)(last ? n : n + 1) * ctx->C};
-      rc = launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, hout, w.skip, n > 0, B, L, st, nullptr, &ub);
-      if (rc) return rc;
-      float *t = hin; hin = hout; hout = t;
-      void *u = uin; uin = uout; uout = u;
-    }
-    return 0;
-  }
-#endif
   if (w.gimg) {
     // deferred-skip form (AP_PREC_BF16): every block writes h' and its bf16 g image; after each group of G layers one GEMM adds
     // the group's skip_conv outputs into skip (a plain store for the first group)
@@ -505,7 +467,7 @@ int run_net(ap_ctx *ctx, const float *x, float step, const Ws &w, int B, int L, 
       const int nl = ctx->NL - n0 < G ? ctx->NL - n0 : G;
       for (int n = n0; n < n0 + nl; n++) {
         // (the last layer's h' is never read -- WaveNet.py:131-135 returns the skip sum only: null = leave res_conv and its store out)
-        rc = launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, n + 1 == ctx->NL ? nullptr : hout, nullptr, 0, B, L, st, nullptr, nullptr,
+        rc = launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, n + 1 == ctx->NL ? nullptr : hout, nullptr, 0, B, L, st, nullptr,
                              w.gimg + (size_t)(n - n0) * w.gslot);
         if (rc) return rc;
         float *t = hin; hin = hout; hout = t;
@@ -565,7 +527,7 @@ extern "C" int ap_resblock_fwd_gate(ap_ctx *ctx, int layer, const float *h_in, c
                                     void *g_image, int B, int L, void *stream) {
   if (int e = check_block_args("ap_resblock_fwd_gate", ctx, h_in && part_t_layer && g_image, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   if (ctx->cfg.precision != AP_PREC_BF16) { set_error("ap_resblock_fwd_gate: AP_PREC_BF16 only"); return -22; }
-  return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, nullptr, g_image);
+  return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, g_image);
 }
 
 extern "C" int ap_resblock_fwd_u_save(ap_ctx *ctx, int layer, const void *u_in, const float *part_t_next, void *u_out, void *g_image,
@@ -584,7 +546,7 @@ extern "C" int ap_resblock_fwd_gate_save(ap_ctx *ctx, int layer, const float *h_
                                          void *g_image, void *gate_factors, int B, int L, void *stream) {
   if (int e = check_block_args("ap_resblock_fwd_gate_save", ctx, h_in && part_t_layer && g_image && gate_factors, layer, B, L, h_in, "h_in", h_out, "h_out")) return e;
   if (ctx->cfg.precision != AP_PREC_BF16) { set_error("ap_resblock_fwd_gate_save: AP_PREC_BF16 only"); return -22; }
-  return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, nullptr, g_image, gate_factors);
+  return launch_resblock(ctx, layer, h_in, part_t_layer, h_out, nullptr, 0, B, L, (hipStream_t)stream, nullptr, g_image, gate_factors);
 }
 
 extern "C" int ap_skip_gemm(ap_ctx *ctx, int layer0, int n_layers, const void *g_images, float *skip, int accumulate_skip,

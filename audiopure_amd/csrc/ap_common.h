@@ -92,7 +92,6 @@ struct ap_ctx {
   float *w1p, *w2p, *wf1p;  // packed fp32 MFMA A-operand images
   void *w1p_bf, *w2p_bf;    // packed bf16 images (AP_PREC_BF16), own allocation
   void *wf1p_bf;            // final conv's first 1x1 as a bf16 image (same allocation)
-  void *w1q_bf;             // GEMM1 image for v_mfma_f32_16x16x32_bf16 (same allocation, behind wf1p_bf)
   void *slab_bf;
   void *w1p_s, *w2p_s;      // 3-way bf16-split images (AP_PREC_F32_SPLIT), own allocation
   void *w1w_s;              // ... and the F(2,3)-transformed, 3-way-split GEMM1 image of ap_resblock_f32s2.hip (same allocation)
@@ -169,17 +168,8 @@ namespace ap {
 int launch_fold_and_pack(ap_ctx *ctx, const float *blob, hipStream_t st);
 int launch_embed(ap_ctx *ctx, float step, float *part_t, hipStream_t st);
 int launch_init_conv(ap_ctx *ctx, const float *x, float *h, int B, int L, hipStream_t st);
-// AP_PREC_BF16 chain form: bf16 images of u = h + part_t, [clip][C / 32][L][32] (ap_resblock_bf16p.hip, UB); `out` is null on the
-// net's last layer, `pt_next` is the next layer's part_t
-struct UbArgs {
-  const void *in;
-  void *out;
-  const float *pt_next;
-};
-int launch_make_ub(const float *h, const float *pt, void *ub, int B, int C, int L, hipStream_t st);
 int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                    int accumulate, int B, int L, hipStream_t st, float *aout = nullptr, const UbArgs *ub = nullptr, void *gout = nullptr,
-                    void *fout = nullptr);
+                    int accumulate, int B, int L, hipStream_t st, float *aout = nullptr, void *gout = nullptr, void *fout = nullptr);
 int launch_final_affine(ap_ctx *ctx, const float *skip, const float *x, float *eps_out, float *out, float ca,
                         float cb, float cs, const float *z, uint64_t seed, uint32_t draw, uint64_t utt_offset,
                         int B, int L, hipStream_t st);
@@ -195,9 +185,9 @@ int launch_final_affine_bf16(ap_ctx *ctx, const float *skip, const float *x, flo
 bool resblock_bf16s_serves(const ap_ctx *ctx, int B, int L);
 int launch_resblock_bf16s(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, void *gout, int B, int L, hipStream_t st);
 int launch_resblock_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                         int accumulate, int B, int L, hipStream_t st, const UbArgs *ub = nullptr, void *gout = nullptr, void *fout = nullptr);
+                         int accumulate, int B, int L, hipStream_t st, void *gout = nullptr, void *fout = nullptr);
 int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                          int accumulate, int B, int L, hipStream_t st, const UbArgs *ub = nullptr, void *gout = nullptr, void *fout = nullptr);   // persistent form; returns 1 if the shape is not served
+                          int accumulate, int B, int L, hipStream_t st, void *gout = nullptr, void *fout = nullptr);   // persistent form; returns 1 if the shape is not served
                                                                   // (fout, with gout: + the gate's derivative factors, 128 KB per 128-sample tile)
 // AP_PREC_BF16_STORE (ap_resblock_bf16u.hip): the residual stream as bf16 images of u = h + part_t, [clip][C / 32][L][32]
 bool resblock_bf16u_serves(const ap_ctx *ctx, int L);

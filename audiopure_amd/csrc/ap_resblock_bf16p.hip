@@ -1,7 +1,7 @@
 // AP_PREC_BF16, persistent form: fused Residual_block.forward (WaveNet.py:75-97) with bf16 MFMA operands, fp32 accumulate,
 // fp32 activations in HBM -- the same arithmetic and the same packed weight images as tools/csrc/ap_resblock_bf16.hip (outputs are
 // bit-identical: tools/cmp_bf16_kernels.py), every dilation (d <= 32 stages one 192-column window per chunk for the three taps), restructured
-// around what the round-2 ablations measured (tools/dbg_resblock_bf16.py):
+// around what the round-2 ablations measured (docs/HISTORY.md):
 //
 //   * with GEMM1 emptied the old kernel still took 52 % of its time, and 60 % of THAT was the residual / skip
 //     read-modify-write traffic (262 KB of loads + 262 KB of stores per 128-sample tile) issued in two bursts at the very
@@ -98,26 +98,6 @@ __global__ void pack_wf1_bf16_kernel(const float *__restrict__ wf1f, __bf16 *__r
   out[idx] = (__bf16)wf1f[(size_t)o * S + k];
 }
 
-// GEMM1 image for v_mfma_f32_16x16x32_bf16: [wave C/32][chunk C/32][k-step of 32 = tap 3][rowtile16 4][lane 64][8]; row tiles
-// 0, 1 = tanh rows 0-15, 16-31 of the wave's 32 gate channels, 2, 3 = sigmoid rows; lane l: row l & 15, k = 8 (l >> 4) + jj,
-// i.e. channel ch*32 + 8 (l >> 4) + jj of tap s -- the same k order inside a chunk as the 32x32x16 image (tap-major).
-__global__ void pack_w1q_bf16_kernel(const float *__restrict__ w1f, __bf16 *__restrict__ out, int C) {
-  const int NW = C / 32, NCH = C / KC_;
-  size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  size_t total = (size_t)NW * NCH * 3 * 4 * 64 * 8;
-  if (idx >= total) return;
-  int jj = idx & 7;
-  int lane = (idx >> 3) & 63;
-  int rt = (idx >> 9) & 3;
-  size_t rest = idx >> 11;
-  int tap = rest % 3; rest /= 3;
-  int ch = rest % NCH;
-  int w = rest / NCH;
-  int c = ch * KC_ + 8 * (lane >> 4) + jj;
-  int o = (rt >> 1) * C + 32 * w + 16 * (rt & 1) + (lane & 15);
-  out[idx] = (__bf16)w1f[((size_t)o * C + c) * 3 + tap];
-}
-
 int launch_pack_bf16(ap_ctx *ctx, hipStream_t st) {
   const int C = ctx->C, S = ctx->S, NL = ctx->NL;
   for (int n = 0; n < NL; n++) {
@@ -125,8 +105,6 @@ int launch_pack_bf16(ap_ctx *ctx, hipStream_t st) {
     pack_w1_bf16_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(ctx->w1f + n * n1, (__bf16 *)ctx->w1p_bf + n * n1, C,
                                                                              ctx->cfg.precision == AP_PREC_BF16_STORE ? 1 : 0);
     pack_w2_bf16_kernel<<<(unsigned)((n2 + 255) / 256), 256, 0, st>>>(ctx->w2f + n * n2, (__bf16 *)ctx->w2p_bf + n * n2, C);
-    if (ctx->w1q_bf && C == 256)
-      pack_w1q_bf16_kernel<<<(unsigned)((n1 + 255) / 256), 256, 0, st>>>(ctx->w1f + n * n1, (__bf16 *)ctx->w1q_bf + n * n1, C);
   }
   if (ctx->wf1p_bf && S % 64 == 0)
     pack_wf1_bf16_kernel<<<(unsigned)(((size_t)S * S + 255) / 256), 256, 0, st>>>(ctx->wf1f, (__bf16 *)ctx->wf1p_bf, S);
@@ -134,67 +112,13 @@ int launch_pack_bf16(ap_ctx *ctx, hipStream_t st) {
   return 0;
 }
 
-#ifdef AP_TOOLS
-// u = bf16(h + part_t) as the chain's operand image [clip][C / 32][L][32] (layer 0 of a sweep; every later layer's image is
-// written by the previous layer's epilogue).  Lane = (sample, channel octet): eight reads L apart (each 64 B per 16 lanes),
-// one 16-byte store; a wave writes 1 KB contiguous.
-__global__ __launch_bounds__(256) void make_ub_kernel(const float *__restrict__ h, const float *__restrict__ pt,
-                                                      __bf16 *__restrict__ ub, int C, int L, size_t total) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // ((clip * C/32 + chunk) * L + t) * 4 + octet
-  if (idx >= total) return;
-  const int oct = (int)(idx & 3);
-  const size_t row = idx >> 2;                                    // (clip * C/32 + chunk) * L + t
-  const int t = (int)(row % (size_t)L);
-  const size_t bc = row / (size_t)L;                              // clip * C/32 + chunk
-  const int c0 = (int)(bc % (size_t)(C / 32)) * 32 + oct * 8;
-  const float *hp = h + ((bc / (size_t)(C / 32)) * C + c0) * (size_t)L + t;
-  u32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; e++) {
-    const f32x2 v2 = {hp[(size_t)(2 * e) * L] + pt[c0 + 2 * e], hp[(size_t)(2 * e + 1) * L] + pt[c0 + 2 * e + 1]};
-    o[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(v2, bf16x2));
-  }
-  reinterpret_cast<u32x4 *>(ub)[idx] = o;
-}
-
-int launch_make_ub(const float *h, const float *pt, void *ub, int B, int C, int L, hipStream_t st) {
-  const size_t total = (size_t)B * (C / 32) * L * 4;
-  make_ub_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(h, pt, (__bf16 *)ub, C, L, total);
-  AP_HIP(hipGetLastError());
-  return 0;
-}
-
-__device__ unsigned long long *g_ptrace = nullptr;               // DBG 2048: [workgroup][wave][64] s_memtime stamps of one tile
-#endif
-
-// DBG (tools builds only; outputs wrong by construction): 1 no weight loads in GEMM1's loop, 2 no X loads, 4 no pack,
-// 8 no GEMM1 MFMA, 16 no B-fragment LDS reads, 32 no gate math, 64 no GEMM2 MFMA, 128 no read-modify-write loads,
-// 256 no stores, 512 no per-chunk barrier, 1024 every tile stages the same 128 columns of clip 0, 2048 phase stamps, 0x2000 no priority swap,
-// 0x4000 default cache policy instead of nt (exact), 0x8000 contiguous walk inside a clip for every dilation (exact).
+// Instantiated: 7 staging forms (WS = 0, 1, 2, -1 for clip lengths that are a multiple of four; 1, 2, -1 ragged) x 5 block forms
+// (fused, DS, DS + NOH, DS + SAVEF, DS + NOH + SAVEF) = 35 kernels, all picked in launch_resblock_bf16p.  The timing-only masks, the
+// 16x16x32 GEMM1 and the operand-image chain this kernel once carried are recorded, with their results, in docs/HISTORY.md.
 // RAG: clip lengths that are not a multiple of four.  Channel rows are then only 4-byte aligned (16-byte accesses at 4-byte
 // aligned addresses are exact on this chip: tools/micro/unaligned_b128.hip), the clip's last column quad is partly outside
 // it: staged samples are zeroed one by one (the quad's count of valid samples instead of one mask), and the epilogue stores
 // of that quad are one to three dwords.
-// M16 (instantiated in the tools library only): GEMM1 on v_mfma_f32_16x16x32_bf16 -- 16-row x 16-column tiles, 32 k per instruction,
-// weight image w1q (pack_w1q), the same X image read with the 16 x 4 lane pattern (224-byte rows: conflict-free), accumulators 4 x 8
-// tiles of 4 registers; gate, GEMM2, epilogues unchanged.  Outputs are BIT-IDENTICAL to the 32x32x16 form (the matrix pipe's fp32
-// accumulation does not depend on how k is grouped into instructions) and the launch is 5-6 % SLOWER (5.44 against 5.12 ms at
-// B = 256: twice the MFMA issue slots, a fragment ring of 32 registers in a kernel that had none to spare); the -6 % of the
-// timing-only substitution (DBG 0x100000: two 16x16x32 on the SAME operand registers per 32x32x16) came from operand reuse, which
-// a real tiling does not have.  DESIGN.md 3.4.
-// UB (round 3 experiment, instantiated in the tools library only; ap_capi.hip run_net under tools bit 0x400000): the GEMM1 operand
-// comes ready-made.  Beside h' (fp32, what the residual
-// and the next layer's residual need) the first epilogue writes ub' = bf16(h' + part_t of the NEXT layer) -- the value the next
-// layer's staging would compute, so the two forms are bit-identical -- as [clip][32-channel chunk][sample][32 channels]: a chunk's
-// (column, tap) operand is one 64-byte run, staged with a 16-byte load + ds_write_b128 per lane (three per thread and chunk for
-// every dilation and every clip length: no FiLM add / convert / mask in the loop, no alignment cases, 24.6 KB per chunk on the
-// CU's memory path instead of 64), out-of-clip taps read through an out-of-range offset (zeros).  A wave's first-pass rows are
-// exactly one chunk, so its ub' stores are contiguous 2 KB runs.  Layer 0's image comes from make_ub_kernel.  Result: eps of the
-// 36-layer sweep BIT-IDENTICAL to the layer-wise form (L = 16000, 4001, 1002, 643, 130), each launch +1 %, the sweep +3 %
-// (tools/ab_bf16_ub.py, profiles/r3_bf16_operand_images_experiment.txt): the block runs at the board's 1400 W power cap
-// (tools/power_check.py), and 64 KB of extra stores per tile cost more energy than 0.3 MB less on the L2 -> CU path and the
-// pack's VALU save.  (The "no X requests / no pack" ablations that promised 13-25 % leave the X image CONSTANT: what they measure
-// is the matrix pipe's data-dependent power, not the staging -- tools/power_ablate_bf16.py.)
 // DS (round 4, "deferred skip"): the block writes h' (fp32) and the gate output g as the bf16 image GEMM2 consumes anyway --
 // [clip][sample][256 channels], 512 B per sample, lossless for the skip sum because skip_conv only ever sees bf16(g) -- and does
 // NOT run the skip half of GEMM2 or its read-modify-write of `skip`.  skipgemm_bf16_kernel (ap_skipgemm_bf16.hip) adds
@@ -207,41 +131,30 @@ __device__ unsigned long long *g_ptrace = nullptr;               // DBG 2048: [w
 // x 16 bytes (128 KB per tile): one 16-byte store per lane and (column tile, q), 1 KB contiguous per wave; the backward's gate kernel has
 // the same wave / lane / register geometry and reads them back the same way (ap_resblock_bwd_bf16.hip).  h' and the g image are
 // bit-identical to the launch without it.
-template <int DBG, int WS = -1, bool RAG = false, bool M16 = false, bool UB = false, bool DS = false, bool NOH = false, bool SAVEF = false>   // WS >= 0: window staging (d <= 32); WS = d mod 4 as far as the code needs it: 0, 1 (d = 1), 2 (d = 2)
+template <int WS, bool RAG, bool DS = false, bool NOH = false, bool SAVEF = false>   // WS >= 0: window staging (d <= 32); WS = d mod 4 as far as the code needs it: 0, 1 (d = 1), 2 (d = 2)
 __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     const float *__restrict__ hin, const float *__restrict__ pt, float *__restrict__ hout, float *__restrict__ skip,
     const void *__restrict__ wbase, unsigned wbytes, unsigned w1_off, unsigned w2_off,        // bf16 weight images (one slab)
     const void *__restrict__ bbase, unsigned bbytes, unsigned b1_off, unsigned b2_off,        // fp32 bias vectors (one slab)
     int L, int d, int accumulate, int ntiles, int nblk,
-    const void *__restrict__ ubin, void *__restrict__ ubout, const float *__restrict__ ptn,     // UB: bf16 operand images in / out (out may be null), the next layer's part_t
-    void *__restrict__ gout,                                                                    // DS: this layer's g image [clip][L][256] bf16
-    void *__restrict__ fout = nullptr) {                                                        // SAVEF: the gate's derivative factors
+    void *__restrict__ fout,                                                                    // SAVEF: the gate's derivative factors
+    void *__restrict__ gout) {                                                                  // DS: this layer's g image [clip][L][256] bf16 (last: next to nblk
+                                                                                                // its kernarg load is merged with nblk's and the prologue's SGPRs renumbered)
   constexpr int C = 256, NW = 8, NCH = C / KC_, NKS = C / 16;
-  static_assert(!SAVEF || (DS && !M16), "SAVEF: a form of the deferred-skip block");
-  static_assert(!UB || (WS < 0 && !M16), "UB: one staging form");
-  static_assert(!DS || (!UB && !M16), "DS: the product staging forms only");
+  static_assert(!SAVEF || DS, "SAVEF: a form of the deferred-skip block");
   static_assert(!NOH || DS, "NOH: a form of the deferred-skip block");
   // cache policy: nt (aux bit 1) on the once-touched streams (the running skip rows in, both outputs out) and on the residual's
   // re-read of h (it hits what is still there and allocates nothing on a miss).  Only the tap loads and the weights allocate in
   // the XCD's L2, so h rows stay until the neighbouring tiles' taps and the residual have read them again: L2-miss reads 27.2 ->
-  // 19.4 GB per 512-clip launch (traffic 1.31 -> 1.08 x algorithmic), -3 % time.  DBG 0x4000: default policy everywhere.
-  constexpr int NT = (DBG & 0x4000) ? 0 : 2;
-  // store policy experiments (tools): DBG 0x1000000 default, 0x2000000 sc0 + nt, 0x3000000 sc1 + nt, 0x5000000 sc1 (agent scope write-through)
-  constexpr int NTS = (DBG & 0x7000000) == 0x1000000 ? 0 : (DBG & 0x7000000) == 0x2000000 ? 3 : (DBG & 0x7000000) == 0x3000000 ? 18 : (DBG & 0x7000000) == 0x5000000 ? 16 : NT;
+  // 19.4 GB per 512-clip launch (traffic 1.31 -> 1.08 x algorithmic), -3 % time.
+  constexpr int NT = 2;
   constexpr bool WIN = WS >= 0;
-  // M16 without the window: 224-byte rows and no swizzle -- with the 16 x 4 lane pattern of the 16x16x32 B fragment the 16-lane groups
-  // of ds_read_b128 are conflict-free iff the row stride is 14 (or 2) slots of 16 B mod 16 (208 B = 13 slots is 2-way); the
-  // pack's ds_write_b128 is 2-way there (16 LDS cycles against the 13 its register transfer takes: measured free in round 2).
-  // The window variants keep 208-byte rows (their scratch column quad leaves no LDS for longer ones).
-  constexpr int XS = (M16 && !WIN) ? 112 : BF_XS;
-  constexpr int SWZ = ((M16 && !WIN) || UB) ? 0 : 1;            // (UB: column pairs four apart per ds_write_b128 group -- conflict-free unswizzled)
-  constexpr int XBYTES = (PT_ + (WIN ? 4 : 0)) * XS * 2;        // 26,624 B per X buffer (WIN: + a scratch column quad), two buffers
+  constexpr int XBYTES = (PT_ + (WIN ? 4 : 0)) * BF_XS * 2;     // 26,624 B per X buffer (WIN: + a scratch column quad), two buffers
   constexpr int GOFF = 2 * XBYTES;
   constexpr int POFF = GOFF + PT_ * BF_GS * 2;                   // output patches: 8 waves x 32 x 32 fp32
   constexpr int PTOFF = POFF + NW * 32 * PS_ * 4;              // part_t (C floats)
   constexpr int BOFF = PTOFF + C * 4;                          // b1 (2C floats: filter | gate rows), b2 (2C: res | skip rows)
-  constexpr int PNOFF = BOFF + 4 * C * 4;                      // UB: the next layer's part_t (C floats)
-  constexpr int LDS_BYTES = PNOFF + (UB ? C * 4 : 0);
+  constexpr int LDS_BYTES = BOFF + 4 * C * 4;
   static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
   __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
 
@@ -282,14 +195,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   // cg&3, oct, cg>>2 so a load covers whole 64-B runs per channel row.  Waves 6, 7 repeat tap 2.
   const int xtap = min(wave >> 1, 2);
   const int cg = ((wave & 1) * 4 + (lane >> 4)) * 4 + (lane & 3), oct = (lane >> 2) & 3;
-  int xcol = 4 * cg, xk = (xtap * KC_ + oct * 8) ^ (SWZ * ((__builtin_popcount(cg & 7) & 1) << 4));   // ^: the X image's 32-byte swizzle (below)
-  // (M16: both, and xwb below, are re-derived from the lane id in pack_ptv -- kept from here they are spilled, and a scratch
-  //  reload in the chunk loop is a vector-memory load whose wait drains every request in flight)
+  const int xcol = 4 * cg, xk = (xtap * KC_ + oct * 8) ^ ((__builtin_popcount(cg & 7) & 1) << 4);   // ^: the X image's 32-byte swizzle (below)
 
   if (tid < C) reinterpret_cast<float *>(lds + PTOFF)[tid] = pt[tid];
-  if constexpr (UB) {
-    if (tid < C) reinterpret_cast<float *>(lds + PNOFF)[tid] = ubout ? ptn[tid] : 0.f;
-  }
   // the bias vectors live in LDS for the whole kernel: fetched per tile from memory they sat behind the previous tile's
   // stores in the in-order vmcnt queue, kept in registers they spilled
   {
@@ -308,7 +216,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   auto tile_bt = [&](int tile, int &b, int &t0) {
     b = __builtin_amdgcn_readfirstlane(tile / ntiles);
     int p = tile % ntiles;
-    if ((DBG & 0x8000) == 0 && wstep > 1) {
+    if (wstep > 1) {
       const int cut = wrem * (wq + 1);
       const int r = p < cut ? p / (wq + 1) : wrem + (p - cut) / wq;
       const int k = p < cut ? p % (wq + 1) : (p - cut) % wq;
@@ -329,7 +237,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   Keep keep;
   const int sq = min(wave, 5) * 8 + (lane >> 3), wc4 = lane & 7;
   unsigned xwb[WIN ? 3 : 1][WIN ? 2 : 1];                      // [tap][first / second image quad of the unit's samples]
-  auto calc_xwb = [&](int sq_, int wc4_) {
+  auto calc_xwb = [&](int sq_, int wc4_) {                     // (a lambda with by-value arguments: written inline, the prologue's VALU order changes)
     if constexpr (WIN) {
 #pragma unroll
       for (int T = 0; T < 3; T++) {
@@ -338,31 +246,13 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
         for (int h2 = 0; h2 < 2; h2++) {
           const int q = qa + h2;
           const int qc = (q >= 0 && q < PT_ / 4) ? q : PT_ / 4;
-          xwb[T][h2] = (unsigned)(4 * qc * (XS * 2) + ((T * 2 * KC_ + wc4_ * 8) ^ ((__builtin_popcount(qc & 7) & 1) << 5)));
+          xwb[T][h2] = (unsigned)(4 * qc * (BF_XS * 2) + ((T * 2 * KC_ + wc4_ * 8) ^ ((__builtin_popcount(qc & 7) & 1) << 5)));
         }
       }
     }
   };
   calc_xwb(sq, wc4);
-  // UB staging unit: thread = (column 16 wave + cw, channel octet ln & 3) for the three taps; cw pairs columns four apart inside
-  // an 8-lane ds_write_b128 group (832 B apart = 16 banks: conflict-free), a wave's load is 16 columns x 64 B = 1 KB contiguous
-  unsigned xv[UB ? 3 : 1];                                       // byte offsets of the three taps' rows inside the clip's image
-  u32x4 xq[UB ? 3 : 1];
-  auto ub_col = [&](int ln) { const int q = ln >> 2; return 16 * wave + (((q & 1) << 2) | ((q >> 1) & 3) | (q & 8)); };
-  auto x_geom = [&](int t0_in, unsigned &voff, Keep &k) {
-    const int t0 = (DBG & 1024) ? 8192 : t0_in;                  // timing-only: every tile stages the same 128 columns of clip 0
-    if constexpr (UB) {
-      int ln;
-      asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-      const int col = ub_col(ln);
-#pragma unroll
-      for (int i = 0; i < 3; i++) {
-        const int t = t0 + col + (i - 1) * d;
-        xv[i] = (t >= 0 && t < L) ? (unsigned)(t * 64 + (ln & 3) * 16) : 0x80000000u;     // outside the clip: zeros (WaveNet.py:26-27)
-      }
-      (void)voff; (void)k;
-      return;
-    }
+  auto x_geom = [&](int t0, unsigned &voff, Keep &k) {
     // the lane's geometry is re-derived from a lane id read here (volatile asm: not hoisted out of the tile loop): kept from
     // the prologue it was spilled, and a scratch reload waits with vmcnt(0) -- here, behind the first epilogue's stores
     int ln;
@@ -388,50 +278,29 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       }
     }
   };
-  const __amdgpu_buffer_rsrc_t hrs_clip0 = clip_rsrc(hin, 0);
-  auto issue_x1 = [&](const __amdgpu_buffer_rsrc_t &rs_in, unsigned voff, int ch, int e) {       // channel e of chunk ch
-    if constexpr (DBG & 2) return;
-    const __amdgpu_buffer_rsrc_t &rs = (DBG & 1024) ? hrs_clip0 : rs_in;      // timing-only: every tile stages clip 0 (cache-resident X)
+  (void)clip_rsrc(hin, 0);                                       // (unused; kept: without it the prologue's scalar instructions come out in another order)
+  auto issue_x1 = [&](const __amdgpu_buffer_rsrc_t &rs, unsigned voff, int ch, int e) {          // channel e of chunk ch
     // (bit_cast the whole vector: element-wise bit_cast of the builtin's int vector is mis-folded to a splat)
     const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, (ch * KC_ + e) * L * 4, 0));
 #pragma unroll
     for (int i = 0; i < 4; i++) xr[e * 4 + i] = v[i];
   };
-  auto issue_x = [&](const __amdgpu_buffer_rsrc_t &rs_in, unsigned voff, int ch) {
-    if constexpr (UB) {                                          // rs_in: the clip's bf16 image; chunk ch = L x 64 bytes
-      if constexpr (DBG & 2) return;
-#pragma unroll
-      for (int i = 0; i < 3; i++) xq[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, xv[i], ch * L * 64, 0));
-      (void)voff;
-    } else if constexpr (WIN) {
+  auto issue_x = [&](const __amdgpu_buffer_rsrc_t &rs, unsigned voff, int ch) {
+    if constexpr (WIN) {
       if (wave < 6) {                                            // wave-uniform
 #pragma unroll
-        for (int e = 0; e < 4; e++) issue_x1(rs_in, voff, ch, e);
+        for (int e = 0; e < 4; e++) issue_x1(rs, voff, ch, e);
       }
     } else {
 #pragma unroll
-      for (int e = 0; e < 8; e++) issue_x1(rs_in, voff, ch, e);
+      for (int e = 0; e < 8; e++) issue_x1(rs, voff, ch, e);
     }
   };
   float ptv8[8];
   u32x4 pkq;
-  unsigned xwa = 0;                                             // UB: this thread's place in an X buffer (tap 0), re-derived per chunk
   auto pack_ptv = [&](int ch) {
     int ln;                                                     // (lane id read here, not kept: see x_geom)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-    if constexpr (UB) {
-      xwa = (unsigned)((ub_col(ln) * XS + (ln & 3) * 8) * 2);
-      (void)ch;
-      return;
-    }
-    if constexpr (M16) {                                        // the pack's LDS addresses live from here to the chunk's last piece only
-      if constexpr (WIN) calc_xwb(min(wave, 5) * 8 + (ln >> 3), ln & 7);
-      else {
-        const int cg_ = ((wave & 1) * 4 + (ln >> 4)) * 4 + (ln & 3), oct_ = (ln >> 2) & 3;
-        xcol = 4 * cg_;
-        xk = (xtap * KC_ + oct_ * 8) ^ (SWZ * ((__builtin_popcount(cg_ & 7) & 1) << 4));
-      }
-    }
     if constexpr (WIN) {
       const float4 p0 = *reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(lds + PTOFF) + (ln & 7) * 4 + ch * KC_);
       ptv8[0] = p0.x; ptv8[1] = p0.y; ptv8[2] = p0.z; ptv8[3] = p0.w;
@@ -448,12 +317,6 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   //   WIN:  sample i: piece 0 = 4 adds, 2 cvt_pk, 2 and (four channels); piece 1 = its three ds_write_b64 (taps -d, 0, +d).
   auto pack_piece = [&](unsigned char *dst, const Keep &keep, auto i_tag, auto hf_tag) {
     constexpr int i = decltype(i_tag)::value, hf = decltype(hf_tag)::value;
-    if constexpr (DBG & 4) return;
-    if constexpr (UB) {                                          // pieces (0,0), (1,0), (2,0): tap i's 16 bytes straight into the image
-      if constexpr (hf == 0 && i < 3) *reinterpret_cast<u32x4 *>(dst + xwa + i * (KC_ * 2)) = xq[i];
-      (void)keep;
-      return;
-    }
     // RAG: keep.m[0] counts the quad's valid samples -> all ones for sample i iff i < count
     const unsigned km = RAG ? (unsigned)(((int)i - (int)keep.m[0]) >> 31) : keep.m[0];
     if constexpr (WIN) {
@@ -470,7 +333,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
             // place of sample 0 inside its image quad: tap -d: d mod 4; centre: 0; tap +d: (-d) mod 4
             const int a0 = WS == 0 || T == 1 ? 0 : (T == 0 ? WS : 4 - WS);
             const int pos = a0 + i;
-            *reinterpret_cast<uint2 *>(dst + xwb[T][pos >> 2] + (pos & 3) * (XS * 2)) = make_uint2(pkq[0], pkq[1]);
+            *reinterpret_cast<uint2 *>(dst + xwb[T][pos >> 2] + (pos & 3) * (BF_XS * 2)) = make_uint2(pkq[0], pkq[1]);
           }
         }
       }
@@ -480,7 +343,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
         pkq[e2] = __builtin_bit_cast(unsigned, __builtin_convertvector(
                                                    f32x2{xr[(2 * e2) * 4 + i] + ptv8[2 * e2],
                                                          xr[(2 * e2 + 1) * 4 + i] + ptv8[2 * e2 + 1]}, bf16x2)) & km;
-      if constexpr (hf == 1) *reinterpret_cast<u32x4 *>(dst + ((xcol + i) * XS + xk) * 2) = pkq;
+      if constexpr (hf == 1) *reinterpret_cast<u32x4 *>(dst + ((xcol + i) * BF_XS + xk) * 2) = pkq;
     }
   };
   auto pack_all = [&](unsigned char *dst, const Keep &keep, int ch) {
@@ -518,18 +381,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   // of ds_read_b128 ({0-3,12-15,20-27}, {4-11,16-19,28-31}: MI355X_MICROARCH.md, LDS) each hold rows of ONE parity, so the
   // reads stay the conflict-free permutation they were (a swap keyed on a single column bit made them 2-way: measured).
   // Cost: one VGPR (a base for even and one for odd k-steps).
-  // M16: image [wave][chunk][k32 step 3][rowtile16 4][lane][8] -> fragment fidx of this wave = fidx KB from the wave's base
-  auto ld_w1q = [&](int fidx) {
-    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, w1_off + (wave * NCH * 12 + fidx) * 1024, 0));
-  };
-  // M16 B-fragment read: lane (c16 = lane & 15, q4 = lane >> 4) takes k-octet 4 s + q4 of column 16 ct16 + c16; the image's 32-byte
-  // swizzle swaps octets o <-> o ^ 2 in columns whose bits 2..4 have odd parity: bits 2, 3 come from c16, bit 4 from ct16 & 1
-  const int c16 = lane & 15, q4 = lane >> 4;
-  const int par16 = __builtin_popcount((c16 >> 2) & 3) & 1;
-  const int rd16e = (c16 * XS) * 2 + ((q4 ^ (SWZ * 2 * par16)) * 16);           // even ct16
-  const int rd16o = (c16 * XS) * 2 + ((q4 ^ (SWZ * 2 * (par16 ^ 1))) * 16);     // odd ct16
-  const int rdoff = (j * XS + 8 * hh) * 2;                      // this lane's B-fragment byte offset inside an X buffer
-  const int rdsw = SWZ * (__builtin_popcount((j >> 2) & 7) & 1) * 32;
+  const int rdoff = (j * BF_XS + 8 * hh) * 2;                     // this lane's B-fragment byte offset inside an X buffer
+  const int rdsw = (__builtin_popcount((j >> 2) & 7) & 1) * 32;
   const unsigned char *gb = lds + GOFF + (j * BF_GS + 8 * hh) * 2;
   float *patch = reinterpret_cast<float *>(lds + POFF) + wave * 32 * PS_;
   const float RS = 0.707106781186547524f;
@@ -538,14 +391,6 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   int b_cur, t0_cur;
   tile_bt(t_first, b_cur, t0_cur);
   __amdgpu_buffer_rsrc_t hrs = clip_rsrc(hin, b_cur);
-  auto ub_rsrc = [&](const void *base, int b) {                  // a clip's bf16 image: [C / 32][L][32]
-    const uint64_t hb = (uint64_t)base + (uint64_t)b * ((uint64_t)C * (uint64_t)L * 2u);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)hb);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(hb >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, (int)(clip_bytes / 2u), 0x00020000);
-  };
-  __amdgpu_buffer_rsrc_t urs = UB ? ub_rsrc(ubin, b_cur) : hrs;
-#define AP_XRS (UB ? urs : hrs)
   unsigned xvoff;
   x_geom(t0_cur, xvoff, keep);
   // a tile's first X chunk and first weight fragments are requested at the END of the previous tile, ahead of that tile's
@@ -554,62 +399,24 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   constexpr int RING = 3, PK = 3;                                // fragment ring depth (k-steps), k-step that carries the pack (a ring of
                                                                  // six with the pack in k-step 5 -- a chunk of lead for X -- measured +2 %)
   bf16x8 w[RING][2];                                                // GEMM1 fragment ring: k-step ks of a chunk uses w[ks % RING][row tile]
-  bf16x8 wfq[2][4];                                                  // M16: ring of two k-steps of 32 (four 16-row fragments each)
   auto tile_head = [&]() {
-    if constexpr (M16) {
-#pragma unroll
-      for (int s2 = 0; s2 < 2; s2++)
-#pragma unroll
-        for (int rt = 0; rt < 4; rt++) wfq[s2][rt] = ld_w1q(s2 * 4 + rt);
-    } else {
 #pragma unroll
     for (int ks = 0; ks < RING; ks++)
 #pragma unroll
       for (int rt = 0; rt < 2; rt++) w[ks][rt] = ld_w1(ks * 2 + rt);
-    }
     pack_all(lds, keep, 0);
-    issue_x(AP_XRS, xvoff, 1);                                   // chunk 1: packed in chunk 0's fourth k-step
+    issue_x(hrs, xvoff, 1);                                   // chunk 1: packed in chunk 0's fourth k-step
   };
-  issue_x(AP_XRS, xvoff, 0);
+  issue_x(hrs, xvoff, 0);
   __syncthreads();                                               // part_t, biases visible
   tile_head();
 
-  int tile_iter = 0;
-  auto mark = [&](int i) {
-#ifdef AP_TOOLS
-    if constexpr (DBG & 2048) {
-      if (tile_iter == 6) {                                      // the 7th tile of every workgroup: steady state
-        __builtin_amdgcn_sched_barrier(0);
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        if (lane == 0) g_ptrace[((size_t)blockIdx.x * NW + wave) * 64 + i] = t;
-        if (i == 0 || i == 32) {                                 // wall clock (100 MHz) beside the shader clock: their ratio is the
-          unsigned long long rt;                                 // clock the chip holds under this kernel
-          asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt)::"memory");
-          if (lane == 0) g_ptrace[((size_t)blockIdx.x * NW + wave) * 64 + 40 + (i == 32)] = rt;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-#endif
-  };
-  auto mark_half = [&](int ch) { mark(ch < NCH - 1 ? 3 + ch * 3 : 24); };
 #pragma unroll 1
-  for (int tile = t_first; tile < t_end; tile += t_step, tile_iter++) {
-    mark(0);
+  for (int tile = t_first; tile < t_end; tile += t_step) {
     const int t0 = t0_cur;
     const int ntile = tile + t_step;
     // ================================================ GEMM1 =========================================================
     f32x16 acc[2][4];
-    f32x4 acq[4][8];                                              // M16: [rowtile16][coltile16]; lane: column c16, rows 4 q4 + reg
-    if constexpr (M16) {
-#pragma unroll
-      for (int rt = 0; rt < 4; rt++) {
-        const f32x4 bv4 = *reinterpret_cast<const f32x4 *>(lds + BOFF + ((rt >> 1) * C + 32 * wave + 16 * (rt & 1) + 4 * q4) * 4);
-#pragma unroll
-        for (int ct = 0; ct < 8; ct++) acq[rt][ct] = bv4;
-      }
-    } else
 #pragma unroll
     for (int rt = 0; rt < 2; rt++)
 #pragma unroll
@@ -623,27 +430,13 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
           acc[rt][ct][4 * q + 3] = bv4[3];
         }
       }
-    mark(1);
     __syncthreads();
-    mark(2);
 
     auto mf = [&](const bf16x8 &a, const bf16x8 &bq, int rt, int ct) {
-      if constexpr (DBG & 8) {
-        asm volatile("" ::"v"(a), "v"(bq));
-      } else if constexpr (DBG & 0x100000) {                   // timing only: the same FLOPs as two v_mfma_f32_16x16x32_bf16 (results wrong)
-        f32x4 lo = __builtin_shufflevector(acc[rt][ct], acc[rt][ct], 0, 1, 2, 3);
-        f32x4 hi = __builtin_shufflevector(acc[rt][ct], acc[rt][ct], 4, 5, 6, 7);
-        lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq, lo, 0, 0, 0);
-        hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bq, hi, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; i++) { acc[rt][ct][i] = lo[i]; acc[rt][ct][4 + i] = hi[i]; }
-      } else {
-        acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq, acc[rt][ct], 0, 0, 0);
-      }
+      acc[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bq, acc[rt][ct], 0, 0, 0);
     };
     auto rdb = [&](bf16x8 &dst, const unsigned char *xbe, const unsigned char *xbo, int ct, int ks) {   // ks: k-step 0..5 of the chunk
-      if constexpr (DBG & 16) asm volatile("" : "=v"(dst));
-      else dst = *reinterpret_cast<const bf16x8 *>(((ks & 1) ? xbo : xbe) + (32 * ct) * (XS * 2) + ks * 32);
+      dst = *reinterpret_cast<const bf16x8 *>(((ks & 1) ? xbo : xbe) + (32 * ct) * (BF_XS * 2) + ks * 32);
     };
     float pre[4][16];
     unsigned evoff[4];                                          // E4 mapping: lane = (row lane>>3 (+8 per step), column quad lane&7)
@@ -658,16 +451,11 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     };
     auto load_pre = [&](const __amdgpu_buffer_rsrc_t &rs, auto ct_tag) {
       constexpr int ct = decltype(ct_tag)::value;
-      if constexpr (DBG & 128) {
 #pragma unroll
-        for (int r = 0; r < 16; r++) pre[ct][r] = 0.f;
-      } else {
+      for (int p = 0; p < 4; p++) {
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, evoff[ct], 8 * p * L * 4, NT));
 #pragma unroll
-        for (int p = 0; p < 4; p++) {
-          const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, evoff[ct], 8 * p * L * 4, NT));
-#pragma unroll
-          for (int i = 0; i < 4; i++) pre[ct][4 * p + i] = v[i];
-        }
+        for (int i = 0; i < 4; i++) pre[ct][4 * p + i] = v[i];
       }
     };
     // One chunk = six k-steps of eight MFMAs in explicit order (pinned with sched_barrier): column-tile-major pairs share one
@@ -681,7 +469,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     // No spilled value may be reloaded inside the tile loop: a scratch reload is a vector-memory load, its wait is
     // s_waitcnt vmcnt(0), and that drains every request in flight (the round's earlier builds had one per chunk).
     // The two waves of a SIMD: the older one (waves 0-3) wins every issue conflict and reached the chunk barrier ~1.2 k cycles
-    // ahead of the younger one, which then finished alone with its stalls exposed (tools/trace_resblock_bf16p.py): the
+    // ahead of the younger one, which then finished alone with its stalls exposed (profiles/r2_bf16_phase_trace.txt): the
     // younger wave gets the priority in k-steps 0-2, the older one (by age) in 3-5.
     auto chunk = [&](const unsigned char *xbe, const unsigned char *xbo, int ch, unsigned char *pdst, auto kind_tag) {
       constexpr int KIND = decltype(kind_tag)::value;            // 0: chunks 0..NCH-3, 1: NCH-2 (no X request), 2: NCH-1
@@ -689,19 +477,13 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       bf16x8 bv[4];
 #pragma unroll
       for (int ct = 0; ct < 4; ct++) rdb(bv[ct], xbe, xbo, ct, 0);
-      if constexpr (!(DBG & 0x2000)) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
+      if (wave >= 4) __builtin_amdgcn_s_setprio(1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int ks = 0; ks < 6; ks++) {
-        const bool reload = !(DBG & 1) && (ks + RING < 6 || !LAST);     // (ring 3) k-steps 3-5 fetch the next chunk's first three
+        const bool reload = ks + RING < 6 || !LAST;                  // (ring 3) k-steps 3-5 fetch the next chunk's first three
         const int nfrag = ks + RING < 6 ? ch * 12 + (ks + RING) * 2 : (ch + 1) * 12 + (ks + RING - 6) * 2;
-        if (ks == 3) {
-          if constexpr (!(DBG & 0x2000)) __builtin_amdgcn_s_setprio(0);
-          mark_half(ch);
-        }
-        if constexpr ((DBG & 2048) != 0 && (DBG & 0x8000000) != 0) {   // tools: stamps 42..47 = start of chunk 3's k-steps (DBG 2048 + 0x8000000)
-          if (ch == 3) mark(42 + ks);
-        }
+        if (ks == 3) __builtin_amdgcn_s_setprio(0);
         if (ks == PK) {
           if constexpr (!LAST) pack_ptv(ch + 1);
           __builtin_amdgcn_sched_barrier(0);
@@ -727,102 +509,27 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
           }
           if (ct == 3 && reload) w[ks % RING][1] = ld_w1(nfrag + 1);
           if constexpr (WITH_X) {
-            if (ks == 5 && ct == 3) issue_x(AP_XRS, xvoff, ch + 2);
+            if (ks == 5 && ct == 3) issue_x(hrs, xvoff, ch + 2);
           }
           __builtin_amdgcn_sched_barrier(0);
         }
       }
     };
 
-    // M16 chunk: three k-steps of 32 (one per tap), each 8 column tiles x 4 row tiles = 32 MFMAs of 16 cycles.  Four B fragments are
-    // held at a time: a column tile's fragment is re-read for column tile + 4 (then for the next k-step) right behind its four
-    // MFMAs.  A k-step's four weight fragments die with its last column tile and are replaced there by those of the k-step two
-    // on (ring of two k-steps = 32 registers; slot = (3 ch + s) & 1, so the chunk loop runs in pairs with the phase a constant).
-    // The middle k-step carries the next chunk's pack (one piece per column tile), the X request goes out behind the last MFMA.
-    auto chunk16 = [&](const unsigned char *xb, int ch, unsigned char *pdst, auto kind_tag, auto ph_tag) {
-      constexpr int KIND = decltype(kind_tag)::value, PH = decltype(ph_tag)::value;
-      constexpr bool LAST = KIND == 2, WITH_X = KIND == 0;
-      auto rdb16 = [&](bf16x8 &dst, int ct, int s2) {
-        dst = *reinterpret_cast<const bf16x8 *>(xb + ((ct & 1) ? rd16o : rd16e) + (16 * ct) * (XS * 2) + s2 * 64);
-      };
-      bf16x8 bv[4];
-#pragma unroll
-      for (int c = 0; c < 4; c++) rdb16(bv[c], c, 0);
-      if constexpr (!(DBG & 0x2000)) { if (wave >= 4) __builtin_amdgcn_s_setprio(1); }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int s2 = 0; s2 < 3; s2++) {
-        const int slot = (PH + s2) & 1;
-        const bool reload = s2 + 2 < 3 || !LAST;                // k-steps 1, 2 fetch the next chunk's first two
-        const int nf = s2 + 2 < 3 ? (ch * 3 + s2 + 2) * 4 : ((ch + 1) * 3 + s2 + 2 - 3) * 4;
-        if (s2 == 1) {
-          if constexpr (!(DBG & 0x2000)) __builtin_amdgcn_s_setprio(0);
-          if constexpr (!LAST) pack_ptv(ch + 1);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int ct = 0; ct < 8; ct++) {
-#pragma unroll
-          for (int rt = 0; rt < 4; rt++) {
-            acq[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfq[slot][rt], bv[ct & 3], acq[rt][ct], 0, 0, 0);
-            if (ct == 7 && reload) wfq[slot][rt] = ld_w1q(nf + rt);
-            if constexpr (!LAST) {
-              if (s2 == 1 && rt == 1) {
-                if (ct == 0) pack_piece(pdst, keep, I0{}, I0{});
-                if (ct == 1) pack_piece(pdst, keep, I0{}, I1{});
-                if (ct == 2) pack_piece(pdst, keep, I1{}, I0{});
-                if (ct == 3) pack_piece(pdst, keep, I1{}, I1{});
-                if (ct == 4) pack_piece(pdst, keep, I2{}, I0{});
-                if (ct == 5) pack_piece(pdst, keep, I2{}, I1{});
-                if (ct == 6) pack_piece(pdst, keep, I3{}, I0{});
-                if (ct == 7) pack_piece(pdst, keep, I3{}, I1{});
-              }
-            }
-            if (rt == 3) {
-              if (ct < 4) rdb16(bv[ct & 3], ct + 4, s2);
-              else if (s2 < 2) rdb16(bv[ct & 3], ct - 4, s2 + 1);
-            }
-            if constexpr (WITH_X) {
-              if (s2 == 2 && ct == 7 && rt == 3) issue_x(AP_XRS, xvoff, ch + 2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        }
-      }
-    };
-    if constexpr (M16) {
-      static_assert(!M16 || NCH == 8, "paired chunk schedule");
-#pragma unroll 1
-      for (int ch = 0; ch < NCH - 2; ch += 2) {
-        chunk16(lds, ch, lds + XBYTES, I0{}, I0{});
-        __syncthreads();
-        chunk16(lds + XBYTES, ch + 1, lds, I0{}, I1{});
-        __syncthreads();
-      }
-      chunk16(lds, NCH - 2, lds + XBYTES, I1{}, I0{});
-      __syncthreads();
-      chunk16(lds + XBYTES, NCH - 1, nullptr, I2{}, I1{});
-    } else {
 #pragma unroll 1
     for (int ch = 0; ch < NCH - 2; ch++) {
       const unsigned char *xbe = lds + (ch & 1) * XBYTES + rdoff + rdsw, *xbo = xbe - 2 * rdsw;
       chunk(xbe, xbo, ch, lds + ((ch + 1) & 1) * XBYTES, I0{});
-      mark(4 + ch * 3);
-      if constexpr (!(DBG & 512)) __syncthreads();              // DBG 512 (timing only): no per-chunk barrier
-      mark(5 + ch * 3);
+      __syncthreads();
     }
     {
       const unsigned char *xbe = lds + ((NCH - 2) & 1) * XBYTES + rdoff + rdsw, *xbo = xbe - 2 * rdsw;
       chunk(xbe, xbo, NCH - 2, lds + ((NCH - 1) & 1) * XBYTES, I1{});
-      mark(4 + (NCH - 2) * 3);
-      if constexpr (!(DBG & 512)) __syncthreads();
-      mark(5 + (NCH - 2) * 3);
+      __syncthreads();
     }
     {
       const unsigned char *xbe = lds + ((NCH - 1) & 1) * XBYTES + rdoff + rdsw, *xbo = xbe - 2 * rdsw;
       chunk(xbe, xbo, NCH - 1, nullptr, I2{});
-      mark(25);
-    }
     }
 
     // ================================================ gate ==========================================================
@@ -864,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     float pre1[4][16];                                           // the running skip rows pass 1 adds into
     auto load_pre1 = [&](auto ct_tag) {
       constexpr int ct = decltype(ct_tag)::value;
-      if ((DBG & 128) || !accumulate) {
+      if (!accumulate) {
 #pragma unroll
         for (int r = 0; r < 16; r++) pre1[ct][r] = 0.f;
       } else {
@@ -880,25 +587,6 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       constexpr int ct = decltype(ct_tag)::value;
       int ln;                                                    // (lane id read here, not kept: see x_geom)
       asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-      if constexpr (M16) {                                       // the two 16-column tiles of this 32-column tile x both channel halves
-        const int c16 = ln & 15, q4 = ln >> 4;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; h2++)
-#pragma unroll
-          for (int rtp = 0; rtp < 2; rtp++) {
-            const f32x4 a4 = acq[rtp][2 * ct + h2], b4 = acq[rtp + 2][2 * ct + h2];
-            unsigned pk[2];
-#pragma unroll
-            for (int e = 0; e < 4; e += 2) {
-              const f32x2 a2 = {a4[e], a4[e + 1]}, b2 = {b4[e], b4[e + 1]};
-              const f32x2 g2 = (DBG & 32) ? a2 + b2 : gate_fast2(a2, b2);
-              pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
-            }
-            *reinterpret_cast<uint2 *>(lds + GOFF + ((32 * ct + 16 * h2 + c16) * BF_GS + 32 * wave + 16 * rtp + 4 * q4) * 2) = make_uint2(pk[0], pk[1]);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-        return;
-      }
       const int j = ln & 31, hh = ln >> 5;
 #pragma unroll
       for (int qq = 0; qq < 4; qq++) {
@@ -916,7 +604,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
             fq[e] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{f1[0], f2[0]}, f16x2));       // (tanh factor, sigmoid factor) of element e
             fq[e + 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{f1[1], f2[1]}, f16x2));
           } else {
-            g2 = (DBG & 32) ? a2 + b2 : gate_fast2(a2, b2);
+            g2 = gate_fast2(a2, b2);
           }
           pk[e >> 1] = __builtin_bit_cast(unsigned, __builtin_convertvector(g2, bf16x2));
         }
@@ -928,7 +616,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
               __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)fhi << 32) | flo), 0, (int)((unsigned)ntiles * 131072u), 0x00020000);
           // (the whole offset in the VGPR, soffset = 0: a >8-byte buffer store with an SGPR soffset reads its data late and the compiler
           //  does not guard the next write of those VGPRs -- the torn lanes of round 1, seen again here in the window-staging instantiations)
-          __builtin_amdgcn_raw_buffer_store_b128(fq, frs, (unsigned)ln * 16u + (unsigned)((((t0 / PT_) * 8 + wave) * 16 + ct * 4 + qq) * 1024), 0, NTS);
+          __builtin_amdgcn_raw_buffer_store_b128(fq, frs, (unsigned)ln * 16u + (unsigned)((((t0 / PT_) * 8 + wave) * 16 + ct * 4 + qq) * 1024), 0, NT);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -950,9 +638,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       load_a4(p1, 4);
     }
     __builtin_amdgcn_sched_barrier(0);
-    mark(26);
     __syncthreads();
-    mark(27);
 
     // ================================================ GEMM2 =========================================================
     // two passes of 32 rows x 128 columns: pass 0 = res_conv rows -> h', pass 1 = skip_conv rows -> skip (WaveNet.py:93-97,:133)
@@ -979,14 +665,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
         rdg(nxt, ks + 1);
 #pragma unroll
         for (int ct = 0; ct < 4; ct++) {
-          if constexpr (DBG & 64) asm volatile("" ::"v"(a), "v"(use[ct]));
-          else if constexpr (DBG & 0x100000) {
-            f32x4 lo = __builtin_shufflevector(ac[ct], ac[ct], 0, 1, 2, 3), hi = __builtin_shufflevector(ac[ct], ac[ct], 4, 5, 6, 7);
-            lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, use[ct], lo, 0, 0, 0);
-            hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, use[ct], hi, 0, 0, 0);
-#pragma unroll
-            for (int i = 0; i < 4; i++) { ac[ct][i] = lo[i]; ac[ct][4 + i] = hi[i]; }
-          } else ac[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, use[ct], ac[ct], 0, 0, 0);
+          ac[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, use[ct], ac[ct], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
       };
@@ -1003,10 +682,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     };
     // epilogue of a pass: MFMA layout (4 rows x 1 column per lane) -> wave-private LDS patch -> 1 row x 4 columns per lane,
     // so the stores (like the operand loads) are 16 B per lane
-    const __amdgpu_buffer_rsrc_t uors = UB ? ub_rsrc(ubout, b_cur) : hrs;
     auto epilogue = [&](const f32x16(&ac)[4], const float(&add)[4][16], const __amdgpu_buffer_rsrc_t &dst, float scale,
                         auto first_tag) {
-      constexpr bool UBW = UB && decltype(first_tag)::value;     // pass 0 of the chain's form also writes the next layer's operand image
 #pragma unroll
       for (int ct = 0; ct < 4; ct++) {
         if constexpr (decltype(first_tag)::value && !DS) {      // pass 0: the h-patch registers of tiles 0, 1 are free again
@@ -1025,45 +702,17 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
           o[3] = (add[ct][4 * p + 3] + v.w) * scale;
           // row step in the VGPR offset, soffset = 0: a >8-byte buffer store with an SGPR soffset reads its data late and
           // the compiler does not guard the next write of those VGPRs (observed in round 1: torn lanes)
-          if constexpr (DBG & 256) asm volatile("" ::"v"(o));
-          else if constexpr (RAG) {
+          if constexpr (RAG) {
             const int nv = L - (t0 + 32 * ct + 4 * (lane & 7));  // valid samples of this lane's column quad (>= 4: all)
             const unsigned so = evoff[ct] + (unsigned)(8 * p * L * 4);
             const u32x4 ou = __builtin_bit_cast(u32x4, o);       // (whole-vector bit_cast: element-wise it is mis-folded to a splat)
-            if (nv >= 4) __builtin_amdgcn_raw_buffer_store_b128(ou, dst, so, 0, NTS);
+            if (nv >= 4) __builtin_amdgcn_raw_buffer_store_b128(ou, dst, so, 0, NT);
             else {
               if (nv >= 1) __builtin_amdgcn_raw_buffer_store_b32(ou[0], dst, so, 0, NT);
               if (nv >= 2) __builtin_amdgcn_raw_buffer_store_b32(ou[1], dst, so + 4u, 0, NT);
               if (nv >= 3) __builtin_amdgcn_raw_buffer_store_b32(ou[2], dst, so + 8u, 0, NT);
             }
-          } else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), dst, evoff[ct] + (unsigned)(8 * p * L * 4), 0, NTS);
-          if constexpr (UBW) {                                  // h' + part_t(next layer) back into the patch, in place
-#pragma clang fp contract(off)                                  // the sum of the ROUNDED h' and part_t, as the next layer's staging forms it: (add + v) * scale + pn as one fma
-                                                                // is a different number (seen: the non-ragged instantiation contracted it, the ragged one did not)
-            const float pn = reinterpret_cast<const float *>(lds + PNOFF)[32 * wave + (lane >> 3) + 8 * p];
-            *reinterpret_cast<float4 *>(patch + ((lane >> 3) + 8 * p) * PS_ + 4 * (lane & 7)) = make_float4(o[0] + pn, o[1] + pn, o[2] + pn, o[3] + pn);
-          }
-        }
-        if constexpr (UBW) {
-          // column j of the patch, channels 16 hh .. 16 hh + 15 -> 32 bytes of ub'[clip][chunk = wave][t0 + 32 ct + j][.]
-          asm volatile("" ::: "memory");                          // (the patch is written and read through different types: keep the order)
-          if (ubout) {                                           // (uniform; null on the net's last layer)
-            u32x4 lo4, hi4;
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-              const f32x2 v2 = {patch[(16 * hh + 2 * e) * PS_ + j], patch[(16 * hh + 2 * e + 1) * PS_ + j]};
-              const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(v2, bf16x2));
-              if (e < 4) lo4[e] = pk; else hi4[e - 4] = pk;
-            }
-            const int t = t0 + 32 * ct + j;
-            // (chunk step in the VGPR offset, soffset = 0: see the note on buffer stores above)
-            const unsigned uo = t < L ? (unsigned)((wave * L + t) * 64 + hh * 32) : 0x80000000u;
-            if constexpr (!(DBG & 256)) {
-              __builtin_amdgcn_raw_buffer_store_b128(lo4, uors, uo, 0, 0);
-              __builtin_amdgcn_raw_buffer_store_b128(hi4, uors, uo + 16u, 0, 0);
-            }
-          }
-          asm volatile("" ::: "memory");
+          } else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), dst, evoff[ct] + (unsigned)(8 * p * L * 4), 0, NT);
         }
       }
     };
@@ -1071,11 +720,9 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     if constexpr (!DS) {
       f32x16 ac[4];
       gemm2_loop(ac, 0);
-      mark(28);
       fetch_bias(I1{});                                          // ahead of this pass's stores
       __builtin_amdgcn_sched_barrier(0);
       epilogue(ac, pre, ors, RS, std::true_type{});
-      mark(29);
     }
     __builtin_amdgcn_sched_barrier(0);
 
@@ -1085,9 +732,8 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
     // (unconditional from here: after its last tile a workgroup re-requests that tile's first chunk and drops it -- a
     // conditional request would keep the staging and fragment registers live across the whole tile)
     hrs = clip_rsrc(hin, b_nxt);
-    if constexpr (UB) urs = ub_rsrc(ubin, b_nxt);
     x_geom(t0_nxt, xvoff, keep);
-    issue_x(AP_XRS, xvoff, 0);
+    issue_x(hrs, xvoff, 0);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (DS) {
       // the ONE pass of this form (res_conv rows -> h'), in the place and with the request order the fused form gives its
@@ -1099,9 +745,7 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
       } else {
         f32x16 ac[4];
         gemm2_loop(ac, 0);
-        mark(30);
         tile_head();
-        mark(31);
         __builtin_amdgcn_sched_barrier(0);
         epilogue(ac, pre, ors, RS, std::false_type{});
       }
@@ -1122,41 +766,26 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
           const u32x4 v = *reinterpret_cast<const u32x4 *>(src + 16 * i * (BF_GS * 2));
           const int t = t0 + colw + 16 * i;
           const unsigned off = t < L ? (unsigned)t * 512u + (unsigned)q * 16u : 0x80000000u;   // outside the clip: dropped
-          if constexpr (DBG & 256) asm volatile("" ::"v"(v));
-          else __builtin_amdgcn_raw_buffer_store_b128(v, grs, off, 0, NTS);
+          __builtin_amdgcn_raw_buffer_store_b128(v, grs, off, 0, NT);
         }
       }
-      mark(32);
     } else {
       f32x16 ac[4];
       gemm2_loop(ac, 1);
-      mark(30);
       // no barrier here: the X buffers have been free since the gate's barrier, the g image is next written by the next
       // tile's gate (eight barriers on), and the epilogue only touches this wave's own patch
       tile_head();
-      mark(31);
       __builtin_amdgcn_sched_barrier(0);
       epilogue(ac, pre1, srs, 1.0f, std::false_type{});
-      mark(32);
     }
     b_cur = b_nxt;
     t0_cur = t0_nxt;
   }
 }
 
-#ifdef AP_TOOLS
-extern int g_dbg_bf16;
-}  // namespace ap
-extern "C" int ap_debug_ptrace(void *buf) {                       // device buffer of grid x 8 x 64 u64 (tools/trace_resblock_bf16p.py)
-  unsigned long long *p = (unsigned long long *)buf;
-  return (int)hipMemcpyToSymbol(HIP_SYMBOL(ap::g_ptrace), &p, sizeof(p));
-}
-namespace ap {
-#endif
-
 // -> 0 launched, 1 shape not served by this kernel (caller falls back to the per-tile kernel)
 int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
-                          int B, int L, hipStream_t st, const UbArgs *ub, void *gout, void *fout) {
+                          int B, int L, hipStream_t st, void *gout, void *fout) {
   const int C = ctx->C, S = ctx->S;
   const int d = 1 << (layer % ctx->cfg.dilation_cycle);
   if (C != 256 || S != 256 || L < 1) return 1;
@@ -1174,142 +803,40 @@ int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float 
   const char *wlo = (const char *)ctx->w1p_bf < (const char *)ctx->w2p_bf ? (const char *)ctx->w1p_bf : (const char *)ctx->w2p_bf;
   const unsigned w1_off = (unsigned)((const char *)ctx->w1p_bf - wlo + layer * n1 * 2);
   const unsigned w2_off = (unsigned)((const char *)ctx->w2p_bf - wlo + layer * n2 * 2);
-  const unsigned wbytes = (unsigned)(((size_t)ctx->NL * (n1 + n2) + (size_t)S * S + (ctx->w1q_bf ? (size_t)ctx->NL * n1 : 0)) * 2);   // the whole bf16 slab
+  const unsigned wbytes = (unsigned)(((size_t)ctx->NL * (n1 + n2) + (size_t)S * S) * 2);   // the whole bf16 slab
   const float *blo = ctx->b1 < ctx->b2 ? ctx->b1 : ctx->b2;
   const float *bhi = ctx->b1 < ctx->b2 ? ctx->b2 : ctx->b1;
   const unsigned b1_off = (unsigned)((ctx->b1 - blo + (size_t)layer * 2 * C) * 4);
   const unsigned b2_off = (unsigned)((ctx->b2 - blo + (size_t)layer * (C + S)) * 4);
   const unsigned bbytes = (unsigned)((bhi - blo + (size_t)ctx->NL * 2 * C) * 4);
-#define AP_P_LAUNCH(D)                                                                                                        \
-  resblock_bf16p_kernel<D><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, \
-                                                           b2_off, L, d, accumulate, ntiles, nblk, nullptr, nullptr, nullptr, nullptr)
-#define AP_P_LAUNCH_WIN(D, W)                                                                                                 \
-  resblock_bf16p_kernel<D, W><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1_off, w2_off, blo, bbytes,  \
-                                                              b1_off, b2_off, L, d, accumulate, ntiles, nblk, nullptr, nullptr, nullptr, nullptr)
-#define AP_P_LAUNCH_RAG(W)                                                                                                    \
-  resblock_bf16p_kernel<0, W, true><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1_off, w2_off, blo, bbytes, \
-                                                                    b1_off, b2_off, L, d, accumulate, ntiles, nblk, nullptr, nullptr, nullptr, nullptr)
   if (gout) {                                                    // deferred-skip form: h' + the bf16 g image, no skip GEMM in the block
     if ((size_t)L * 512 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16: clip too long for the bf16 g image"); return -22; }
     if (fout && (size_t)ntiles * 131072 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16: clip too long for the gate-factor image"); return -22; }
-#define AP_P_LAUNCH_DS(W, R)                                                                                                   \
-  do {                                                                                                                         \
-    if (fout && hout) /* the differentiable purifier's forward: + the gate's derivative factors */                             \
-      resblock_bf16p_kernel<0, W, R, false, false, true, false, true><<<(unsigned)grid, 512, 0, st>>>(                         \
-          hin, pt, hout, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d, 0, ntiles, nblk, nullptr, nullptr, nullptr, gout, fout); \
-    else if (fout)                                                                                                             \
-      resblock_bf16p_kernel<0, W, R, false, false, true, true, true><<<(unsigned)grid, 512, 0, st>>>(                          \
-          hin, pt, nullptr, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d, 0, ntiles, nblk, nullptr, nullptr, nullptr, gout, fout); \
-    else if (hout)                                                                                                             \
-      resblock_bf16p_kernel<0, W, R, false, false, true><<<(unsigned)grid, 512, 0, st>>>(                                      \
-          hin, pt, hout, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d, 0, ntiles, nblk, nullptr, nullptr, nullptr, gout); \
-    else /* h' not wanted (the net's last layer) */                                                                            \
-      resblock_bf16p_kernel<0, W, R, false, false, true, true><<<(unsigned)grid, 512, 0, st>>>(                                \
-          hin, pt, nullptr, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d, 0, ntiles, nblk, nullptr, nullptr, nullptr, gout); \
-  } while (0)
-    if (rag) {
-      if (ws == 1) AP_P_LAUNCH_DS(1, true);
-      else if (ws == 2) AP_P_LAUNCH_DS(2, true);
-      else AP_P_LAUNCH_DS(-1, true);
-    } else if (ws == 0) AP_P_LAUNCH_DS(0, false);
-    else if (ws == 1) AP_P_LAUNCH_DS(1, false);
-    else if (ws == 2) AP_P_LAUNCH_DS(2, false);
-    else AP_P_LAUNCH_DS(-1, false);
-#undef AP_P_LAUNCH_DS
-    AP_HIP(hipGetLastError());
-    return 0;
   }
-#ifdef AP_TOOLS
-  if (ub) {                                                      // the operand-image experiment: images in / out, one staging form for every d
-    if ((size_t)C * (size_t)L * 2 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16: clip too long for the bf16 operand image"); return -22; }
-    if (rag)
-      resblock_bf16p_kernel<0, -1, true, false, true><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1_off, w2_off, blo, bbytes,
-                                                                                      b1_off, b2_off, L, d, accumulate, ntiles, nblk, ub->in, ub->out, ub->pt_next, nullptr);
-    else
-      resblock_bf16p_kernel<0, -1, false, false, true><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1_off, w2_off, blo, bbytes,
-                                                                                       b1_off, b2_off, L, d, accumulate, ntiles, nblk, ub->in, ub->out, ub->pt_next, nullptr);
-    AP_HIP(hipGetLastError());
-    return 0;
-  }
-  if (rag) {
-    if (ws == 1) AP_P_LAUNCH_RAG(1);
-    else if (ws == 2) AP_P_LAUNCH_RAG(2);
-    else AP_P_LAUNCH_RAG(-1);
-  } else
-  if (ws >= 0 && !(g_dbg_bf16 & 0x10000)) {                      // tools bit 0x10000: three-tap staging for every d (A/B)
-    if (ws == 0) AP_P_LAUNCH_WIN(0, 0);
-    else if (ws == 1) AP_P_LAUNCH_WIN(0, 1);
-    else AP_P_LAUNCH_WIN(0, 2);
-  } else if (ws > 0) {
-    return 1;                                                    // d = 1, 2 without the window: the per-tile kernel
-  } else
-  if ((g_dbg_bf16 & 0x200000) && ctx->w1q_bf) {                  // tools bit 0x200000: GEMM1 on v_mfma_f32_16x16x32_bf16 (exact; A/B)
-    const unsigned w1q_off = (unsigned)((const char *)ctx->w1q_bf - wlo + layer * n1 * 2);
-    resblock_bf16p_kernel<0, -1, false, true><<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, skip, wlo, wbytes, w1q_off, w2_off, blo,
-                                                                            bbytes, b1_off, b2_off, L, d, accumulate, ntiles, nblk, nullptr, nullptr, nullptr, nullptr);
-  } else
-  if (g_dbg_bf16 & 0x100000) AP_P_LAUNCH(0x100000);             // timing only: v_mfma_f32_16x16x32_bf16 pairs in place of 32x32x16
-  else if ((g_dbg_bf16 & 0x7000000) == 0x1000000) AP_P_LAUNCH(0x1000000);   // store cache policies (exact)
-  else if ((g_dbg_bf16 & 0x7000000) == 0x2000000) AP_P_LAUNCH(0x2000000);
-  else if ((g_dbg_bf16 & 0x7000000) == 0x3000000) AP_P_LAUNCH(0x3000000);
-  else if ((g_dbg_bf16 & 0x7000000) == 0x5000000) AP_P_LAUNCH(0x5000000);
-  else
-  switch (g_dbg_bf16 & 0x800efff) {
-    case 0: AP_P_LAUNCH(0); break;
-    case 1: AP_P_LAUNCH(1); break;
-    case 2: AP_P_LAUNCH(2); break;
-    case 3: AP_P_LAUNCH(3); break;
-    case 4: AP_P_LAUNCH(4); break;
-    case 7: AP_P_LAUNCH(7); break;
-    case 8: AP_P_LAUNCH(8); break;
-    case 16: AP_P_LAUNCH(16); break;
-    case 23: AP_P_LAUNCH(23); break;
-    case 31: AP_P_LAUNCH(31); break;
-    case 31 + 128: AP_P_LAUNCH(31 + 128); break;
-    case 31 + 256: AP_P_LAUNCH(31 + 256); break;
-    case 31 + 384: AP_P_LAUNCH(31 + 384); break;
-    case 128: AP_P_LAUNCH(128); break;
-    case 256: AP_P_LAUNCH(256); break;
-    case 384: AP_P_LAUNCH(384); break;
-    case 384 + 1: AP_P_LAUNCH(384 + 1); break;
-    case 384 + 2: AP_P_LAUNCH(384 + 2); break;
-    case 384 + 3: AP_P_LAUNCH(384 + 3); break;
-    case 384 + 8: AP_P_LAUNCH(384 + 8); break;
-    case 384 + 19: AP_P_LAUNCH(384 + 19); break;
-    case 384 + 23: AP_P_LAUNCH(384 + 23); break;
-
-    case 384 + 31 + 64: AP_P_LAUNCH(384 + 31 + 64); break;
-    case 384 + 31 + 96: AP_P_LAUNCH(384 + 31 + 96); break;
-    case 512: AP_P_LAUNCH(512); break;
-    case 512 + 384: AP_P_LAUNCH(512 + 384); break;
-    case 1024: AP_P_LAUNCH(1024); break;
-    case 2048: AP_P_LAUNCH(2048); break;
-    case 2048 + 384: AP_P_LAUNCH(2048 + 384); break;
-    case 2048 + 0x8000000: AP_P_LAUNCH(2048 + 0x8000000); break;
-    case 1024 + 384: AP_P_LAUNCH(1024 + 384); break;
-    case 0x2000: AP_P_LAUNCH(0x2000); break;
-    case 0x4000: AP_P_LAUNCH(0x4000); break;
-    case 0x8000: AP_P_LAUNCH(0x8000); break;
-    case 32: AP_P_LAUNCH(32); break;
-    case 64: AP_P_LAUNCH(64); break;
-    case 96: AP_P_LAUNCH(96); break;
-    case 32 + 384: AP_P_LAUNCH(32 + 384); break;
-    case 96 + 384: AP_P_LAUNCH(96 + 384); break;
-    default: set_error("no such DBG instantiation"); return -22;
-  }
-#else
+  // one launch of staging form (WS, RAG); the block form follows from the outputs asked for: gout -> DS (skip and accumulate unused),
+  // + no hout -> NOH (the net's last layer), + fout -> SAVEF (the differentiable purifier's forward)
+  auto launch = [&](auto ws_tag, auto rag_tag) {
+    constexpr int W = decltype(ws_tag)::value;
+    constexpr bool R = decltype(rag_tag)::value;
+    auto go = [&](auto *kernel) {
+      kernel<<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, gout ? nullptr : skip, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d,
+                                             gout ? 0 : accumulate, ntiles, nblk, fout, gout);
+    };
+    if (!gout) go(resblock_bf16p_kernel<W, R>);
+    else if (fout && hout) go(resblock_bf16p_kernel<W, R, true, false, true>);
+    else if (fout) go(resblock_bf16p_kernel<W, R, true, true, true>);
+    else if (hout) go(resblock_bf16p_kernel<W, R, true>);
+    else go(resblock_bf16p_kernel<W, R, true, true>);
+  };
+  using std::integral_constant;
   if (rag) {                                                     // (d = 4 .. 32 ragged: the three-tap form, one instantiation fewer)
-    if (ws == 1) AP_P_LAUNCH_RAG(1);
-    else if (ws == 2) AP_P_LAUNCH_RAG(2);
-    else AP_P_LAUNCH_RAG(-1);
-  } else if (ws == 0) AP_P_LAUNCH_WIN(0, 0);
-  else if (ws == 1) AP_P_LAUNCH_WIN(0, 1);
-  else if (ws == 2) AP_P_LAUNCH_WIN(0, 2);
-  else AP_P_LAUNCH(0);
-#endif
-#undef AP_P_LAUNCH
-#undef AP_P_LAUNCH_WIN
-#undef AP_P_LAUNCH_RAG
+    if (ws == 1) launch(integral_constant<int, 1>{}, std::true_type{});
+    else if (ws == 2) launch(integral_constant<int, 2>{}, std::true_type{});
+    else launch(integral_constant<int, -1>{}, std::true_type{});
+  } else if (ws == 0) launch(integral_constant<int, 0>{}, std::false_type{});
+  else if (ws == 1) launch(integral_constant<int, 1>{}, std::false_type{});
+  else if (ws == 2) launch(integral_constant<int, 2>{}, std::false_type{});
+  else launch(integral_constant<int, -1>{}, std::false_type{});
   AP_HIP(hipGetLastError());
   return 0;
 }
@@ -1319,12 +846,12 @@ int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float 
 // (C = S = 256; any dilation of a power-of-two cycle, any clip length).  The one-tile-per-workgroup kernel of round 1
 // (tools/csrc/ap_resblock_bf16.hip) is compiled into the tools library only, as the A/B baseline of tools/cmp_bf16_kernels.py.
 int launch_resblock_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
-                         int B, int L, hipStream_t st, const UbArgs *ub, void *gout, void *fout) {
+                         int B, int L, hipStream_t st, void *gout, void *fout) {
   if (ctx->C != 256 || ctx->S != 256) {
     set_error("AP_PREC_BF16 is built for res_channels = skip_channels = 256 only (got %d / %d)", ctx->C, ctx->S);
     return -22;
   }
-  const int rc = launch_resblock_bf16p(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, ub, gout, fout);
+  const int rc = launch_resblock_bf16p(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, gout, fout);
   if (rc == 1) {
     set_error("AP_PREC_BF16: shape not served (layer %d, L = %d)", layer, L);
     return -22;
