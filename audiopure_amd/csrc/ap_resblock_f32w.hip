@@ -51,8 +51,13 @@ constexpr int NCONST_ = 5 * WC_;           // b1 (2C) | b2 (2C) | part_t (C): th
 // barrier per chunk pair, measured null there and is not in this source):
 constexpr int DIET_CARRY_ = 2;           // the last k-group's wrapped weight loads ARE the next tile's first units; no X request past chunk 7
 constexpr int DIET_CONST_ = 4;           // b1, b2, part_t copied to LDS once per launch: the accumulator inits read LDS, not memory
+// What runs under MFMAs that used to run between them (one more bit, the same A/B: profiles/f32w_edges_ab.txt).  The split is by ROW
+// tiles, so every accumulator keeps its own MFMA sequence and none lives longer than before.  (Bit 8, the last chunk by rows with
+// half of the gate in its second pass, measured slower there and is not in this source: v_mfma_f32_32x32x2_f32 hides LDS and
+// memory instructions but no VALU work -- profiles/f32w_edges_gap_budget.txt.)
+constexpr int DIET_ROWS_ = 16;           // GEMM2: the res rows, then the skip rows with the h' epilogue in their gaps
 #ifndef AP_F32W_DIET
-#define AP_F32W_DIET 6
+#define AP_F32W_DIET 22
 #endif
 // the 4-byte epilogue form (ragged clip lengths) holds 64 residual values across GEMM2 and has no registers to spare: no item
 constexpr int DIET4_ = 0;
@@ -118,6 +123,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     const float *__restrict__ b2, int L, int logd, int accumulate, int ntiles, int nblk, float *__restrict__ aout) {
   constexpr int C = WC_;
   constexpr bool CARRY = (DIET & DIET_CARRY_) != 0, CONST = (DIET & DIET_CONST_) != 0;
+  constexpr bool ROWS = Q16 && !NOH && (DIET & DIET_ROWS_) != 0;                        // every 16-byte form that writes h'
   // LDS map (floats): X sub-buffers 0, 1 | g image | Q16: output patches | CONST: b1, b2, part_t
   constexpr int COFF_ = Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_;
   __shared__ __attribute__((aligned(16))) float lds[COFF_ + (CONST ? NCONST_ : 0)];
@@ -170,9 +176,18 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   };
   // the launch constants for the accumulator inits.  CONST: from their LDS copy -- as buffer loads they queue behind the previous
   // tile's skip stores (vmcnt retires in order) at every tile's top and again before GEMM2
-  auto ld_b1 = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + idx); else return ld4(b1rs, idx); };
-  auto ld_b2 = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + 2 * C + idx); else return ld4(b2rs, idx); };
-  auto ld_pt = [&](int idx) { if constexpr (CONST) return *reinterpret_cast<const f32x4 *>(lds + COFF_ + 4 * C + idx); else return ld4(ptrs, idx); };
+  // (ROWS: through one opaque per-lane base.  The copy lies past byte 65 535, the reach of a DS instruction's offset field, so
+  // from the array's own address every read gets an address register of its own -- thirty of them, hoisted out of the tile loop)
+  // (the index is what is opaque: an opaque pointer would lose its address space)
+  int cbase = COFF_ + 64 * wave + 4 * hh;
+  if constexpr (CONST && ROWS) asm volatile("" : "+v"(cbase));
+  auto ld_c = [&](int idx) {
+    if constexpr (ROWS) return *reinterpret_cast<const f32x4 *>(lds + cbase + (idx - 64 * wave - 4 * hh));
+    else return *reinterpret_cast<const f32x4 *>(lds + COFF_ + idx);
+  };
+  auto ld_b1 = [&](int idx) { if constexpr (CONST) return ld_c(idx); else return ld4(b1rs, idx); };
+  auto ld_b2 = [&](int idx) { if constexpr (CONST) return ld_c(2 * C + idx); else return ld4(b2rs, idx); };
+  auto ld_pt = [&](int idx) { if constexpr (CONST) return ld_c(4 * C + idx); else return ld4(ptrs, idx); };
 
   auto load_a1 = [&](f32x4(&a)[4], unsigned unit) {             // one (k-group, product) unit of GEMM1 weights: 4 row tiles
 #pragma unroll
@@ -398,8 +413,19 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
       }
     }
     f32x4 a2[2][4];                                              // ring of two k-groups (64 MFMAs)
+    f32x4 a2r[4][2];                                             // ROWS: two row tiles per pass, so the same registers hold four k-groups
+    auto load_a2r = [&](f32x4(&a)[2], unsigned soff) {           // soff: k-group kg, row tiles rt0, rt0 + 1 = kg * UNIT_BYTES_ + rt0 * 1024
 #pragma unroll
-    for (int k = 0; k < 2; k++) load_a2(a2[k], (unsigned)k);
+      for (int r = 0; r < 2; r++)
+        a[r] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w2rs, lane16 + r * 1024u, soff, 0));
+    };
+    if constexpr (ROWS) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) load_a2r(a2r[k], (unsigned)k * UNIT_BYTES_);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2; k++) load_a2(a2[k], (unsigned)k);
+    }
 
     // The residual's h patch (this wave's 64 res rows x 64 columns) is requested now -- behind the first weight groups, so that
     // their waits do not include it -- and consumed after GEMM2: the epilogue never waits on memory.
@@ -437,7 +463,106 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     }
     __syncthreads();                                             // g image complete
 
-    {
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    const float RS = 0.707106781186547524f;   // float(math.sqrt(0.5))
+    if constexpr (ROWS) {
+      // ---- GEMM2 by rows: k-groups 0..31 on the two res row tiles, then 0..31 on the two skip row tiles -- every accumulator sees
+      // its k-groups in the order it always did -- and in the gaps of the second pass the four res tiles leave as they do in the
+      // epilogue below (patch write, four ds_read_b128, (hq + v) * RS, 16-byte stores; the patches are wave-private and lie
+      // behind the g image).  A tile's hq registers, free once it has left, take that tile's running skip rows: requested here,
+      // used after the loop (without `accumulate` from a descriptor of no bytes: zeros, no branch).  g fragments are read twice
+      // and a k-group ahead; the weight ring is four k-groups deep (4 k cycles), which also covers the h' stores that are now
+      // older than weight loads in the vmcnt queue.
+      const __amdgpu_buffer_rsrc_t ors = uni_rsrc(hout + (size_t)b * C * L, clip_bytes);
+      const __amdgpu_buffer_rsrc_t sls = uni_rsrc(skip + (size_t)b * C * L, accumulate ? clip_bytes : 0u);
+      const float *gfrag = lds + GOFF_ + j * GS_ + 4 * hh;
+      float *patch0 = lds + POFF_ + wave * (2 * 32 * PS_);
+      const int rowq = lane >> 3, cq = lane & 7;
+      f32x4 bq2[2][2];
+      bq2[0][0] = *reinterpret_cast<const f32x4 *>(gfrag);
+      bq2[0][1] = *reinterpret_cast<const f32x4 *>(gfrag + 32 * GS_);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+      for (int kg4 = 0; kg4 < C / 8; kg4 += 4) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int kn = (kg4 + k + 1) & (C / 8 - 1);            // (the last one wraps: the second pass's first fragments)
+          bq2[(k + 1) & 1][0] = *reinterpret_cast<const f32x4 *>(gfrag + 8 * kn);
+          bq2[(k + 1) & 1][1] = *reinterpret_cast<const f32x4 *>(gfrag + 32 * GS_ + 8 * kn);
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+              for (int ct = 0; ct < 2; ct++)
+                acc2[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2r[k][rt][e], bq2[k & 1][ct][e], acc2[rt][ct], 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const int nx = kg4 + k + 4;                            // (the last four request the skip rows' first four k-groups)
+          load_a2r(a2r[k], nx < C / 8 ? (unsigned)nx * UNIT_BYTES_ : (unsigned)(nx - C / 8) * UNIT_BYTES_ + 2048u);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; t++) {                              // res tile t = (row tile t >> 1, column tile t & 1) leaves under k-groups 8 t ..
+        const int rt = t >> 1, ct = t & 1;
+        float *patch = patch0 + (t & 1) * (32 * PS_);
+        f32x4 pv[4];
+#pragma unroll
+        for (int k8 = 0; k8 < 8; k8++) {
+          const int kg = 8 * t + k8, k = kg & 3;
+          if (kg + 1 < C / 8) {
+            bq2[(kg + 1) & 1][0] = *reinterpret_cast<const f32x4 *>(gfrag + 8 * (kg + 1));
+            bq2[(kg + 1) & 1][1] = *reinterpret_cast<const f32x4 *>(gfrag + 32 * GS_ + 8 * (kg + 1));
+          }
+          if (k8 == 0) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) patch[rowoff(r, hh) * PS_ + j] = acc2[rt][ct][r];
+          }
+          if (k8 == 1) {
+#pragma unroll
+            for (int p = 0; p < 4; p++) pv[p] = *reinterpret_cast<const f32x4 *>(patch + (rowq + 8 * p) * PS_ + 4 * cq);
+          }
+          if (k8 == 2) {
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+              const f32x4 o = (hq[rt][ct][p] + pv[p]) * RS;
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ors, eo4[ct], (32 * rt + 8 * p) * L * 4, 2);
+            }
+          }
+#pragma unroll
+          for (int e = 0; e < 4; e++)
+#pragma unroll
+            for (int r2 = 0; r2 < 2; r2++)
+#pragma unroll
+              for (int c2 = 0; c2 < 2; c2++)
+                acc2[2 + r2][c2] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2r[k][r2][e], bq2[kg & 1][c2][e], acc2[2 + r2][c2], 0, 0, 0);
+          if (k8 == 0) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+            }
+          }
+          if (k8 == 2) {
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x040, 4, 0);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          load_a2r(a2r[k], (unsigned)((kg + 4) & (C / 8 - 1)) * UNIT_BYTES_ + 2048u);   // (the last four wrap: unused)
+          if (k8 == 3) {                                         // behind this k-group's weights: their wait does not include these
+#pragma unroll
+            for (int p = 0; p < 4; p++)
+              hq[rt][ct][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(sls, eo4[ct], (32 * rt + 8 * p) * L * 4, 2));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    } else {
       const float *gfrag = lds + GOFF_ + j * GS_ + 4 * hh;
 #pragma unroll 1
       for (int kg4 = 0; kg4 < C / 8; kg4 += 4) {
@@ -467,10 +592,9 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
       // ---- 16-byte epilogue (WaveNet.py:97, :133).  Order: the running skip rows are requested, the res tiles leave (h'), the NEXT
       // tile's first weights and X chunk are requested, the skip tiles leave -- so the next tile's first wait has only the 16 skip
       // stores behind its loads (vmcnt retires in order).
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-      const float RS = 0.707106781186547524f;   // float(math.sqrt(0.5))
       f32x4 sk4[2][2][4];
-      if (accumulate) {
+      if constexpr (ROWS) {                                      // (requested inside GEMM2, into the hq registers)
+      } else if (accumulate) {
 #pragma unroll
         for (int rt = 0; rt < 2; rt++)
 #pragma unroll
@@ -492,7 +616,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
         for (int p = 0; p < 4; p++) out4(p, *reinterpret_cast<const f32x4 *>(patch + (rowq + 8 * p) * PS_ + 4 * cq));
       };
       {
-        if (!NOH) {
+        if (!NOH && !ROWS) {
 #pragma unroll
           for (int rt = 0; rt < 2; rt++)
 #pragma unroll
@@ -518,7 +642,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #pragma unroll
           for (int ct = 0; ct < 2; ct++)
             leave(2 * rt + ct, acc2[2 + rt][ct], [&](int p, f32x4 v) {
-              const f32x4 o = sk4[rt][ct][p] + v;
+              f32x4 o;
+              if constexpr (ROWS) o = hq[rt][ct][p] + v; else o = sk4[rt][ct][p] + v;
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), srs, eo4[ct], (32 * rt + 8 * p) * L * 4, 2);
             });
       }
@@ -620,7 +745,7 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
     AP_HIP(hipGetLastError());                                                                                                    \
     return 0;                                                                                                                     \
   }
-  if (g_diet != AP_F32W_DIET) { AP_F32W_AB(0) AP_F32W_AB(2) AP_F32W_AB(4) }
+  if (g_diet != AP_F32W_DIET) { AP_F32W_AB(0) AP_F32W_AB(2) AP_F32W_AB(4) AP_F32W_AB(6) AP_F32W_AB(22) }
 #undef AP_F32W_AB
 #endif
   if (hout && q16) resblock_f32w_kernel<false, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
@@ -644,10 +769,10 @@ extern "C" int ap_debug_resblock_f32w(ap_ctx *ctx, int layer, const float *h_in,
                                       int accumulate, int B, int L, void *stream, float *pre_gate) {
   return ap::launch_resblock_f32w(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
 }
-// the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with DIET mask 0, 2, 4 or 6; every other form keeps
+// the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with DIET mask 0, 2, 4, 6 or 22; every other form keeps
 // the product's mask
 extern "C" int ap_debug_f32w_diet(int mask) {
-  if (mask != 0 && mask != 2 && mask != 4 && mask != 6) return -22;
+  if (mask != 0 && mask != 2 && mask != 4 && mask != 6 && mask != 22) return -22;
   ap::g_diet = mask;
   return 0;
 }

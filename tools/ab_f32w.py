@@ -5,6 +5,9 @@
                                              both; B = 256 and 512, layers 0, 5, 11; interleaved repeats; the table goes
                                              to FILE (default profiles/f32w_diet_ab.txt, whose records -- everything from its first
                                              line that starts with "== " -- are kept)
+   python tools/ab_f32w.py --edges [--out FILE]   the h' epilogue under MFMAs: DIET mask 6 (the diet alone) against 22 (GEMM2 by rows, the
+                                             res tiles leaving under the skip rows: the product), the parent kernel beside them;
+                                             same method; default FILE profiles/f32w_edges_ab.txt
    python tools/ab_f32w.py --epilogue [B]    the two epilogue forms: 16-byte stores through LDS patches (clip lengths that are
                                              multiples of four) against the 4-byte form every other length takes"""
 import os
@@ -21,6 +24,16 @@ from audiopure_amd.diffusion_models.DiffWave_Unconditional.WaveNet import WaveNe
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORDS_MARK = "\n== "                                           # the sections tools/ab_f32w.py does not write: kept across runs
 DIET = [("parent", None), ("no item", 0), ("carry", 2), ("const", 4), ("both", 6)]
+EDGES = [("parent", None), ("mask 6", 6), ("rows", 22)]
+PRODUCT_MASK = 22
+DIET_HEAD = ["F(2,3) fp32 block, GEMM1 diet: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1, h' form, one process,",
+             "the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against the parent kernel.",
+             "parent = the kernel before the diet (tools/csrc/ap_resblock_f32w_parent.hip); the others are ap_resblock_f32w.hip with DIET mask",
+             "0 (no item), 2 (carried weight prefetch, no X request past chunk 7), 4 (b1, b2, part_t in LDS), 6 (both).", ""]
+EDGES_HEAD = ["F(2,3) fp32 block, the h' epilogue under MFMAs: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1,",
+              "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 6.",
+              "parent = tools/csrc/ap_resblock_f32w_parent.hip (the kernel before the GEMM1 diet); the others are ap_resblock_f32w.hip with DIET",
+              "mask 6 (the diet alone: the product before this change) and 22 (+ DIET_ROWS_: the product).", ""]
 
 
 def setup(B):
@@ -64,11 +77,8 @@ def epilogue_ab(B):
             print(f"layer {layer:2d}  16-byte epilogue: {t16:7.3f} ms   4-byte epilogue: {t4:7.3f} ms", flush=True)
 
 
-def diet_ab(out):
-    lines = ["F(2,3) fp32 block, GEMM1 diet: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1, h' form, one process,",
-             "the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against the parent kernel.",
-             "parent = the kernel before the diet (tools/csrc/ap_resblock_f32w_parent.hip); the others are ap_resblock_f32w.hip with DIET mask",
-             "0 (no item), 2 (carried weight prefetch, no X request past chunk 7), 4 (b1, b2, part_t in LDS), 6 (both: the product).", ""]
+def diet_ab(out, DIET=DIET, head=DIET_HEAD, base_name="parent"):
+    lines = list(head)
     for B in (256, 512):
         net, eng, (hd, pt, hout, sk, B, L) = setup(B)
         lib = eng.lib
@@ -86,8 +96,8 @@ def diet_ab(out):
                     else:
                         assert lib.ap_debug_f32w_diet(mask) == 0
                         ts[name].append(timer(new))
-            assert lib.ap_debug_f32w_diet(6) == 0
-            base = sorted(ts["parent"])[1]
+            assert lib.ap_debug_f32w_diet(PRODUCT_MASK) == 0
+            base = sorted(ts[base_name])[1]
             for name, _ in DIET:
                 v = sorted(ts[name])
                 lines.append(f"B={B:3d} layer {layer:2d}  {name:8s} {v[1]:8.3f} ms  [{v[0]:8.3f} .. {v[2]:8.3f}]  {100 * (base - v[1]) / base:+6.2f} %")
@@ -109,8 +119,13 @@ def main():
     if "--epilogue" in sys.argv:
         rest = [a for a in sys.argv[1:] if a != "--epilogue"]
         return epilogue_ab(int(rest[0]) if rest else 256)
-    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "f32w_diet_ab.txt")
-    diet_ab(out)
+    edges = "--edges" in sys.argv
+    out = (sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv
+           else os.path.join(ROOT, "profiles", "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
+    if edges:
+        diet_ab(out, EDGES, EDGES_HEAD, "mask 6")
+    else:
+        diet_ab(out)
 
 
 if __name__ == "__main__":
