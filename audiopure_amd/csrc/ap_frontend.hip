@@ -138,9 +138,10 @@ int launch_m5(ap_m5 *m, const float *x, float *logprobs, int B, int L, hipStream
 }
 
 // ---- dL/dx through M5 (white-box attack, white_box_attack.py:392,437-439: loss = CE(classifier(purifier(x)))) ----
-// One workgroup per clip: recompute the four stages keeping, per pooled element, its value and which of the 4 window
-// positions won the max; then fc -> avg-pool -> stage 4..1 backward, each input gradient GATHERED over the outputs
-// that read it (no atomics).  Parameters are frozen (eval): only the input gradient is formed.
+// One workgroup per clip: recompute the four stages keeping, per pooled element, its value and one byte -- which of the 4
+// window positions won the max, or 4 where the ReLU shut the element; then fc -> avg-pool -> stage 4..1 backward, each input
+// gradient GATHERED over the outputs that read it (no atomics).  The backward reads the bytes only, so a stage's gradient
+// takes the place of its activation in LDS.  Parameters are frozen (eval): only the input gradient is formed.
 template <bool FIRST>
 __device__ __forceinline__ void m5_stage_save(const float *in, int Lin, int ci, const float *__restrict__ wT,
                                               const float *__restrict__ bias, int co, int k, int stride, float *out,
@@ -162,13 +163,14 @@ __device__ __forceinline__ void m5_stage_save(const float *in, int Lin, int ci, 
 #pragma unroll
     for (int i = 1; i < 4; i++)
       if (a[i] > a[am]) am = i;                                  // first maximum wins, like nn.MaxPool1d
-    out[(size_t)o * Q + q] = fmaxf(a[am] + bias[o], 0.f);
-    arg[(size_t)o * Q + q] = (unsigned char)am;
+    const float v = a[am] + bias[o];
+    out[(size_t)o * Q + q] = fmaxf(v, 0.f);
+    arg[(size_t)o * Q + q] = (unsigned char)(v > 0.f ? am : 4);      // 4 matches no window position: no gradient
   }
 }
 
 // din[c][j] = sum over outputs (o, pre-pool position p) that read input j and won their pooling window
-__device__ __forceinline__ void m5_stage_bwd(const float *dout, const float *pout, const unsigned char *arg, int Q, int co,
+__device__ __forceinline__ void m5_stage_bwd(const float *dout, const unsigned char *arg, int Q, int co,
                                              const float *__restrict__ wT, int ci, int k, int stride, float *din, int Lin) {
   for (int idx = threadIdx.x; idx < ci * Lin; idx += blockDim.x) {
     const int j = idx % Lin, c = idx / Lin;
@@ -182,7 +184,7 @@ __device__ __forceinline__ void m5_stage_bwd(const float *dout, const float *pou
       const float *wr = wT + ((size_t)c * k + t) * co;
       for (int o = 0; o < co; o++) {
         const size_t e = (size_t)o * Q + q;
-        if (arg[e] == sub && pout[e] > 0.f) s = __builtin_fmaf(wr[o], dout[e], s);
+        if (arg[e] == sub) s = __builtin_fmaf(wr[o], dout[e], s);
       }
     }
     din[idx] = s;
@@ -204,8 +206,8 @@ __global__ __launch_bounds__(1024) void m5_bwd_kernel(const float *__restrict__ 
   const float *xb = x + (size_t)b * L;
   const int n1 = nc * Q1, n2 = nc * Q2, n3 = 2 * nc * Q3, n4 = 2 * nc * Q4;
   float *o1 = sm, *o2 = o1 + n1, *o3 = o2 + n2, *o4 = o3 + n3;          // pooled activations
-  float *g1 = o4 + n4, *g2 = g1 + n1, *g3 = g2 + n2, *g4 = g3 + n3;     // their gradients
-  float *feat = g4 + n4, *logit = feat + 2 * nc, *dlogit = logit + 64;
+  float *g1 = o1, *g2 = o2, *g3 = o3, *g4 = o4;                         // their gradients, each written once its activation is spent
+  float *feat = o4 + n4, *logit = feat + 2 * nc, *dlogit = logit + 64;
   unsigned char *a1 = reinterpret_cast<unsigned char *>(dlogit + 64), *a2 = a1 + n1, *a3 = a2 + n2, *a4 = a3 + n3;
   m5_stage_save<true>(xb, L, 1, w1, b1, nc, k1, stride, o1, a1, Q1);
   __syncthreads();
@@ -241,13 +243,13 @@ __global__ __launch_bounds__(1024) void m5_bwd_kernel(const float *__restrict__ 
     for (int q = 0; q < Q4; q++) g4[c * Q4 + q] = s / (float)Q4;
   }
   __syncthreads();
-  m5_stage_bwd(g4, o4, a4, Q4, 2 * nc, w4, 2 * nc, 3, 1, g3, Q3);
+  m5_stage_bwd(g4, a4, Q4, 2 * nc, w4, 2 * nc, 3, 1, g3, Q3);
   __syncthreads();
-  m5_stage_bwd(g3, o3, a3, Q3, 2 * nc, w3, nc, 3, 1, g2, Q2);
+  m5_stage_bwd(g3, a3, Q3, 2 * nc, w3, nc, 3, 1, g2, Q2);
   __syncthreads();
-  m5_stage_bwd(g2, o2, a2, Q2, nc, w2, nc, 3, 1, g1, Q1);
+  m5_stage_bwd(g2, a2, Q2, nc, w2, nc, 3, 1, g1, Q1);
   __syncthreads();
-  m5_stage_bwd(g1, o1, a1, Q1, nc, w1, 1, k1, stride, dx + (size_t)b * L, L);
+  m5_stage_bwd(g1, a1, Q1, nc, w1, 1, k1, stride, dx + (size_t)b * L, L);
 }
 
 int launch_m5_bwd(ap_m5 *m, const float *x, const float *dlogp, float *dx, int B, int L, hipStream_t st) {
@@ -257,7 +259,7 @@ int launch_m5_bwd(ap_m5 *m, const float *x, const float *dlogp, float *dx, int B
   const int Q2 = (Q1 - 2) / 4, Q3 = (Q2 - 2) / 4, Q4 = (Q3 - 2) / 4;
   if (Q1 < 3 || Q2 < 3 || Q3 < 3 || Q4 < 1) { set_error("m5: clip length %d too short for four conv/pool stages", L); return -22; }
   const size_t act = (size_t)nc * Q1 + (size_t)nc * Q2 + (size_t)2 * nc * Q3 + (size_t)2 * nc * Q4;
-  const size_t smem = (2 * act + 2 * nc + 128) * sizeof(float) + ((act + 15) & ~(size_t)15);
+  const size_t smem = (act + 2 * nc + 128) * sizeof(float) + ((act + 15) & ~(size_t)15);
   if (smem > 160 * 1024) { set_error("m5 backward: clip length %d needs %zu bytes of LDS", L, smem); return -22; }
   static bool attr_set = false;
   if (!attr_set) {
