@@ -76,6 +76,34 @@ __device__ __forceinline__ float gate(float a, float b) {
   return (E - 1.0f) * __builtin_amdgcn_rcpf((E + 1.0f) * (1.0f + F));
 }
 
+// gate() on a pair of values, element for element the same operations (ap_resblock_f32w.hip's 16-byte forms, whose gate phase runs
+// with the matrix pipe idle: a v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 is one issue slot for two gates, each element with the
+// bits of the one-wide instruction).  The clamps and the three transcendentals stay per element.  gate()'s 2 a and -b are folded
+// into exp_acc's constants -- (2 a) c and a (2 c) are the same real number, so every product and fma rounds to the same float:
+// hi, lo = 2 L2E_HI, 2 L2E_LO for E and -L2E_HI, -L2E_LO for F.  No contraction: gate() has no mul feeding an add outside its
+// written fma's, and the pair form must not grow one.
+__device__ __forceinline__ f32x2 exp_acc2(f32x2 x, float hi, float lo) {
+#pragma clang fp contract(off)
+  const f32x2 h2 = {hi, hi}, l2 = {lo, lo};
+  const f32x2 t = x * h2;
+  f32x2 r = __builtin_elementwise_fma(x, h2, -t);
+  r = __builtin_elementwise_fma(x, l2, r);
+  const f32x2 e = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+  return __builtin_elementwise_fma(e, r * 0.693147182464599609375f, e);
+}
+
+__device__ __forceinline__ f32x2 gate2(f32x2 a, f32x2 b) {
+#pragma clang fp contract(off)
+  const float L2E_HI = 1.44269502162933349609375f, L2E_LO = 1.92596299e-8f;   // exp_acc's
+  const f32x2 ac = {fminf(fmaxf(a[0], -15.0f), 15.0f), fminf(fmaxf(a[1], -15.0f), 15.0f)};
+  const f32x2 bc = {fmaxf(b[0], -80.0f), fmaxf(b[1], -80.0f)};
+  const f32x2 E = exp_acc2(ac, 2.0f * L2E_HI, 2.0f * L2E_LO);
+  const f32x2 F = exp_acc2(bc, -L2E_HI, -L2E_LO);
+  const f32x2 den = (E + 1.0f) * (1.0f + F);
+  const f32x2 rc = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+  return (E - 1.0f) * rc;
+}
+
 // ---- the bf16 modes' gate, on a pair of values ---------------------------------------------------------------------------------
 // tanh(a) sigmoid(b) = (1 - E) / ((1 + E)(1 + F)), E = e^(-2a), F = e^(-b).  a is clamped to [-16, 16] first (one v_med3;
 // tanh(+-16) rounds to +-1 in fp32, so the clamp changes no result): E stays finite, the sign comes out of 1 - E, and no

@@ -56,8 +56,15 @@ constexpr int DIET_CONST_ = 4;           // b1, b2, part_t copied to LDS once pe
 // half of the gate in its second pass, measured slower there and is not in this source: v_mfma_f32_32x32x2_f32 hides LDS and
 // memory instructions but no VALU work -- profiles/f32w_edges_gap_budget.txt.)
 constexpr int DIET_ROWS_ = 16;           // GEMM2: the res rows, then the skip rows with the h' epilogue in their gaps
+// Fewer vector-ALU issue slots (beside v_mfma_f32_32x32x2_f32 every one is paid in full; the A/B: profiles/f32w_pk_ab.txt):
+constexpr int DIET_PK_ = 32;             // 16-byte forms: output transform and gate on register pairs (v_pk_add/mul/fma_f32: the matrix pipe is idle there)
+// (Bit 64, staging with out-of-clip taps loaded as +0 and u = fma(pt, 1 or 0, x) in place of add + select, gained 0.23 .. 0.45 % but
+// stayed inside mask 22's min-max band in one of the six cells and is not in this source: docs/HISTORY.md.)
+constexpr int DIET_ZERO_ = 128;          // m1, m3, m4 are not zeroed: chunk 0, peeled, starts them from the instruction's constant 0
+// (with chunk 0 peeled the allocator also stops giving three product tiles other registers in the last chunk than in the chunk loop,
+// which mask 22 pays per tile with 32 v_accvgpr_mov, 80 reads and 80 writes in the last chunk's MFMA gaps: docs/HISTORY.md I.13)
 #ifndef AP_F32W_DIET
-#define AP_F32W_DIET 22
+#define AP_F32W_DIET 182
 #endif
 // the 4-byte epilogue form (ragged clip lengths) holds 64 residual values across GEMM2 and has no registers to spare: no item
 constexpr int DIET4_ = 0;
@@ -124,6 +131,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   constexpr int C = WC_;
   constexpr bool CARRY = (DIET & DIET_CARRY_) != 0, CONST = (DIET & DIET_CONST_) != 0;
   constexpr bool ROWS = Q16 && !NOH && (DIET & DIET_ROWS_) != 0;                        // every 16-byte form that writes h'
+  constexpr bool PK = Q16 && (DIET & DIET_PK_) != 0;
+  constexpr bool ZERO = Q16 && (DIET & DIET_ZERO_) != 0;
   // LDS map (floats): X sub-buffers 0, 1 | g image | Q16: output patches | CONST: b1, b2, part_t
   constexpr int COFF_ = Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_;
   __shared__ __attribute__((aligned(16))) float lds[COFF_ + (CONST ? NCONST_ : 0)];
@@ -278,8 +287,10 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
         acc[1][rt][4 * q + 2] = bv[2];
         acc[1][rt][4 * q + 3] = bv[3];
       }
+      if constexpr (!ZERO) {
 #pragma unroll
-      for (int r = 0; r < 16; r++) acc[0][rt][r] = acc[2][rt][r] = acc[3][rt][r] = 0.f;
+        for (int r = 0; r < 16; r++) acc[0][rt][r] = acc[2][rt][r] = acc[3][rt][r] = 0.f;
+      }
     }
     store_x(lds);
     __syncthreads();
@@ -289,8 +300,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     // last chunk runs a body that requests and stages nothing.
     constexpr int NSTAGE = CARRY ? NCH_ - 1 : NCH_;
     const float *xfrag = lds + j * XS_ + 4 * hh;
-    auto chunk = [&](int ch, auto stage_tag) __attribute__((always_inline)) {
-      constexpr bool STAGE = decltype(stage_tag)::value;
+    auto chunk = [&](int ch, auto stage_tag, auto first_tag) __attribute__((always_inline)) {
+      constexpr bool STAGE = decltype(stage_tag)::value, FIRST = decltype(first_tag)::value;
       const float *xb = xfrag + (ch & 1) * XBUF_;
       if constexpr (STAGE) issue_x(ch + 1 < NCH_ ? ch + 1 : ch);
       f32x4 bq[2];
@@ -308,8 +319,12 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #pragma unroll
           for (int e = 0; e < 4; e++)
 #pragma unroll
-            for (int rt = 0; rt < 4; rt++)
-              acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], acc[comp][rt], 0, 0, 0);
+            for (int rt = 0; rt < 4; rt++) {
+              if (FIRST && kg == 0 && e == 0 && comp != 1)         // (m2 starts from the bias)
+                acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], f32x16{}, 0, 0, 0);
+              else
+                acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], acc[comp][rt], 0, 0, 0);
+            }
           if (STAGE && u == 12) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
@@ -326,14 +341,18 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
         }
       }
     };
+    if constexpr (ZERO) {
+      chunk(0, std::true_type{}, std::true_type{});
+      __syncthreads();
+    }
 #pragma unroll 1
-    for (int ch = 0; ch < NSTAGE; ch++) {
-      chunk(ch, std::true_type{});
+    for (int ch = ZERO ? 1 : 0; ch < NSTAGE; ch++) {
+      chunk(ch, std::true_type{}, std::false_type{});
       __syncthreads();
     }
 #pragma unroll 1
     for (int ch = NSTAGE; ch < NCH_; ch++) {
-      chunk(ch, std::false_type{});
+      chunk(ch, std::false_type{}, std::false_type{});
       __syncthreads();
     }
 
@@ -365,22 +384,53 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #pragma unroll
         for (int q = 0; q < 4; q++) {
           f32x4 v0, v1;
+          if constexpr (PK) {
+            // the same sums, in the same order, and gate2 = gate element for element, on accumulator registers (r, r + 1): two
+            // elements per issue slot, the result pairs the halves of the ds_write_b128 operands
 #pragma unroll
-          for (int e = 0; e < 4; e++) {
-            const int r = 4 * q + e;
-            const float ta = (acc[0][2 * p][r] + acc[1][2 * p][r]) + acc[2][2 * p][r];
-            const float sa = (acc[0][2 * p + 1][r] + acc[1][2 * p + 1][r]) + acc[2][2 * p + 1][r];
-            const float tb = (acc[1][2 * p][r] - acc[2][2 * p][r]) + acc[3][2 * p][r];
-            const float sb = (acc[1][2 * p + 1][r] - acc[2][2 * p + 1][r]) + acc[3][2 * p + 1][r];
-            v0[e] = gate(ta, sa);
-            v1[e] = gate(tb, sb);
-            if constexpr (SAVE) {                                // channel 64 wave + 32 p + rowoff(r, hh), samples of this lane's pair
-              const unsigned so = ((unsigned)(64 * wave + 32 * p + 4 * hh) * (unsigned)L) * 4u;
-              const int ro = rowoff(r, 0) * L * 4;
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ta), ars, so + sv0, ro, 0);
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sa), ars, so + sv0 + (unsigned)C * (unsigned)L * 4u, ro, 0);
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, tb), ars, so + sv1, ro, 0);
-              __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sb), ars, so + sv1 + (unsigned)C * (unsigned)L * 4u, ro, 0);
+            for (int e = 0; e < 4; e += 2) {
+              const int r = 4 * q + e;
+              auto pr = [&](const f32x16 &t) { return f32x2{t[r], t[r + 1]}; };
+              const f32x2 ta = (pr(acc[0][2 * p]) + pr(acc[1][2 * p])) + pr(acc[2][2 * p]);
+              const f32x2 sa = (pr(acc[0][2 * p + 1]) + pr(acc[1][2 * p + 1])) + pr(acc[2][2 * p + 1]);
+              const f32x2 tb = (pr(acc[1][2 * p]) - pr(acc[2][2 * p])) + pr(acc[3][2 * p]);
+              const f32x2 sb = (pr(acc[1][2 * p + 1]) - pr(acc[2][2 * p + 1])) + pr(acc[3][2 * p + 1]);
+              const f32x2 ga = gate2(ta, sa), gb = gate2(tb, sb);
+              v0[e] = ga[0], v0[e + 1] = ga[1];
+              v1[e] = gb[0], v1[e + 1] = gb[1];
+              if constexpr (SAVE) {
+                const unsigned so = ((unsigned)(64 * wave + 32 * p + 4 * hh) * (unsigned)L) * 4u;
+                // (the whole pair, then index: element-wise bit_cast of a vector element mis-folds to a splat)
+                const u32x2 tau = __builtin_bit_cast(u32x2, ta), sau = __builtin_bit_cast(u32x2, sa);
+                const u32x2 tbu = __builtin_bit_cast(u32x2, tb), sbu = __builtin_bit_cast(u32x2, sb);
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                  const int ro = rowoff(r + i, 0) * L * 4;
+                  __builtin_amdgcn_raw_buffer_store_b32(tau[i], ars, so + sv0, ro, 0);
+                  __builtin_amdgcn_raw_buffer_store_b32(sau[i], ars, so + sv0 + (unsigned)C * (unsigned)L * 4u, ro, 0);
+                  __builtin_amdgcn_raw_buffer_store_b32(tbu[i], ars, so + sv1, ro, 0);
+                  __builtin_amdgcn_raw_buffer_store_b32(sbu[i], ars, so + sv1 + (unsigned)C * (unsigned)L * 4u, ro, 0);
+                }
+              }
+            }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+              const int r = 4 * q + e;
+              const float ta = (acc[0][2 * p][r] + acc[1][2 * p][r]) + acc[2][2 * p][r];
+              const float sa = (acc[0][2 * p + 1][r] + acc[1][2 * p + 1][r]) + acc[2][2 * p + 1][r];
+              const float tb = (acc[1][2 * p][r] - acc[2][2 * p][r]) + acc[3][2 * p][r];
+              const float sb = (acc[1][2 * p + 1][r] - acc[2][2 * p + 1][r]) + acc[3][2 * p + 1][r];
+              v0[e] = gate(ta, sa);
+              v1[e] = gate(tb, sb);
+              if constexpr (SAVE) {                                // channel 64 wave + 32 p + rowoff(r, hh), samples of this lane's pair
+                const unsigned so = ((unsigned)(64 * wave + 32 * p + 4 * hh) * (unsigned)L) * 4u;
+                const int ro = rowoff(r, 0) * L * 4;
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ta), ars, so + sv0, ro, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sa), ars, so + sv0 + (unsigned)C * (unsigned)L * 4u, ro, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, tb), ars, so + sv1, ro, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, sb), ars, so + sv1 + (unsigned)C * (unsigned)L * 4u, ro, 0);
+              }
             }
           }
           *reinterpret_cast<f32x4 *>(g0 + 32 * p + 8 * q) = v0;   // channels 64 wave + 32 p + 8 q + 4 hh + (0..3)
@@ -700,6 +750,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 }
 
 #ifdef AP_TOOLS
+// the DIET masks the tools build instantiates beside the product's (each item alone on top of its predecessor's product mask)
+#define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150)
 static int g_no_q16 = 0;                                        // ap_debug_f32w_q16(0): the 4-byte epilogue for every clip length (A/B)
 static int g_diet = AP_F32W_DIET;                               // ap_debug_f32w_diet(mask): the h'-writing Q16 block with another DIET mask (A/B)
 #else
@@ -745,7 +797,7 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
     AP_HIP(hipGetLastError());                                                                                                    \
     return 0;                                                                                                                     \
   }
-  if (g_diet != AP_F32W_DIET) { AP_F32W_AB(0) AP_F32W_AB(2) AP_F32W_AB(4) AP_F32W_AB(6) AP_F32W_AB(22) }
+  AP_F32W_AB_MASKS(AP_F32W_AB)
 #undef AP_F32W_AB
 #endif
   if (hout && q16) resblock_f32w_kernel<false, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
@@ -769,10 +821,15 @@ extern "C" int ap_debug_resblock_f32w(ap_ctx *ctx, int layer, const float *h_in,
                                       int accumulate, int B, int L, void *stream, float *pre_gate) {
   return ap::launch_resblock_f32w(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
 }
-// the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with DIET mask 0, 2, 4, 6 or 22; every other form keeps
+// the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with the product's DIET mask or one of AP_F32W_AB_MASKS
+// (54 = 22 + pairs, 150 = 22 + no zeroing); every other form keeps
 // the product's mask
 extern "C" int ap_debug_f32w_diet(int mask) {
-  if (mask != 0 && mask != 2 && mask != 4 && mask != 6 && mask != 22) return -22;
+  bool known = mask == AP_F32W_DIET;
+#define AP_F32W_KNOWN(M) known = known || mask == M;
+  AP_F32W_AB_MASKS(AP_F32W_KNOWN)
+#undef AP_F32W_KNOWN
+  if (!known) return -22;
   ap::g_diet = mask;
   return 0;
 }

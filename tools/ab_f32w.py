@@ -8,6 +8,10 @@
    python tools/ab_f32w.py --edges [--out FILE]   the h' epilogue under MFMAs: DIET mask 6 (the diet alone) against 22 (GEMM2 by rows, the
                                              res tiles leaving under the skip rows: the product), the parent kernel beside them;
                                              same method; default FILE profiles/f32w_edges_ab.txt
+   python tools/ab_f32w.py --pk [--out FILE]      fewer vector-ALU slots: DIET mask 22 (the product before this change) against each new
+                                             bit alone on top of it -- 54 (pair gate and transform), 150 (no zeroing of m1, m3, m4) --
+                                             and 182 (both: the product); same
+                                             method; default FILE profiles/f32w_pk_ab.txt
    python tools/ab_f32w.py --epilogue [B]    the two epilogue forms: 16-byte stores through LDS patches (clip lengths that are
                                              multiples of four) against the 4-byte form every other length takes"""
 import os
@@ -25,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RECORDS_MARK = "\n== "                                           # the sections tools/ab_f32w.py does not write: kept across runs
 DIET = [("parent", None), ("no item", 0), ("carry", 2), ("const", 4), ("both", 6)]
 EDGES = [("parent", None), ("mask 6", 6), ("rows", 22)]
-PRODUCT_MASK = 22
+PK = [("mask 22", 22), ("pairs", 54), ("zero", 150), ("both", 182)]
+PRODUCT_MASK = 182
 DIET_HEAD = ["F(2,3) fp32 block, GEMM1 diet: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1, h' form, one process,",
              "the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against the parent kernel.",
              "parent = the kernel before the diet (tools/csrc/ap_resblock_f32w_parent.hip); the others are ap_resblock_f32w.hip with DIET mask",
@@ -34,6 +39,10 @@ EDGES_HEAD = ["F(2,3) fp32 block, the h' epilogue under MFMAs: ms per launch (HI
               "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 6.",
               "parent = tools/csrc/ap_resblock_f32w_parent.hip (the kernel before the GEMM1 diet); the others are ap_resblock_f32w.hip with DIET",
               "mask 6 (the diet alone: the product before this change) and 22 (+ DIET_ROWS_: the product).", ""]
+PK_HEAD = ["F(2,3) fp32 block, fewer vector-ALU issue slots: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1,",
+           "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 22.",
+           "ap_resblock_f32w.hip with DIET mask 22 (the product before this change), 54 (+ DIET_PK_: output transform and gate on register",
+           "pairs), 150 (+ DIET_ZERO_: chunk 0 peeled, m1, m3, m4 start from the instruction's constant 0) and 182 (both: the product).", ""]
 
 
 def setup(B):
@@ -119,10 +128,12 @@ def main():
     if "--epilogue" in sys.argv:
         rest = [a for a in sys.argv[1:] if a != "--epilogue"]
         return epilogue_ab(int(rest[0]) if rest else 256)
-    edges = "--edges" in sys.argv
+    edges, pk = "--edges" in sys.argv, "--pk" in sys.argv
     out = (sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv
-           else os.path.join(ROOT, "profiles", "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
-    if edges:
+           else os.path.join(ROOT, "profiles", "f32w_pk_ab.txt" if pk else "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
+    if pk:
+        diet_ab(out, PK, PK_HEAD, "mask 22")
+    elif edges:
         diet_ab(out, EDGES, EDGES_HEAD, "mask 6")
     else:
         diet_ab(out)
