@@ -145,6 +145,13 @@ SIGNATURES = {
     "ap_psy_scratch_elems": (_sz, [_i, _i, _i, _i]),
     "ap_psy_threshold": (_i, [_fp, _vp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
     "ap_psy_loss_grad": (_i, [_fp, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "ap_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ap_wgrad_corr": (_i, [_fp, _fp, _fp, _fp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    "ap_rowsum": (_i, [_fp, _fp, _fp, _fp, _i, _i, _i, _i, _f, _i, _vp]),
+    "ap_rowsum_f64": (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),
+    "ap_embed_bwd_scratch_elems": (_sz, [_vp]),
+    "ap_embed_bwd": (_i, [_vp, _f, _vp] + [_fp] * 8 + [_i, _vp]),
+    "ap_weight_norm_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
 }
 
 _LIB = None

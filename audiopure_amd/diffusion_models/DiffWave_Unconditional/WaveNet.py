@@ -75,6 +75,34 @@ import itertools
 
 _ENGINE_SERIAL = itertools.count(1)
 
+# The library's block kernels are built for 64, 128 and 256 channels.  A narrower net (32 channels: the mini net of the training
+# tests and of the reference's golden vectors) runs as the 64-channel net it is a corner of: the extra channels get zero folded
+# weights (weight_g = 0 over a non-zero weight_v), zero biases and zero FiLM rows, so they carry exact zeros through ReLU(0) = 0 and
+# tanh(0) sigmoid(0) = 0, and the real channels' sums only gain + 0 terms -- the same fp32 results.
+_NATIVE_WIDTH = {32: 64}
+
+
+def _pad_rows(t, C, Cp, halves=1, fill=0.0):
+    """[halves * C, ...] -> [halves * Cp, ...]: every half of the rows padded to Cp with ``fill`` (the dilated conv's rows are a tanh
+    half and a sigmoid half)."""
+    if Cp == C:
+        return t
+    parts = []
+    for h in range(halves):
+        parts += [t[h * C:(h + 1) * C], torch.full((Cp - C,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)]
+    return torch.cat(parts, 0)
+
+
+def _pad_v(t, C, Cp, halves=1):
+    """weight_v [halves * C][C][k] at the native width: zero input channels behind the real rows (their norm is unchanged), all-ones
+    rows for the extra channels (any non-zero direction: their weight_g is 0)."""
+    if Cp == C:
+        return t
+    if t.shape[1] == C:                                          # (the init conv has one input channel: nothing to pad there)
+        zeros = torch.zeros((t.shape[0], Cp - C) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)
+        t = torch.cat([t, zeros], 1)
+    return _pad_rows(t, C, Cp, halves, fill=1.0)
+
 
 class NativeEngine:
     """Owns the ap_ctx, the packed weights on the device and a cached workspace."""
@@ -252,6 +280,30 @@ class WaveNet_Speech_Commands(nn.Module):
         ts += [f0.bias, f0.weight_g, f0.weight_v, f2.weight, f2.bias]
         return ts
 
+    def native_width(self) -> int:
+        """Channels of the native context: res_channels, or the next width the library is built for (_NATIVE_WIDTH)."""
+        C_ = self.config["res_channels"]
+        return _NATIVE_WIDTH.get(C_, C_) if self.config["skip_channels"] == C_ else C_
+
+    def pad_rows(self, t, halves=1):
+        """A per-channel tensor of this network ([halves * C, ...]) at the native width (zero rows for the extra channels)."""
+        return _pad_rows(t, self.config["res_channels"], self.native_width(), halves)
+
+    def _native_tensors(self, ts):
+        """``_blob_tensors()`` as the native context loads them: fp32, at the native width."""
+        C_, Cp = self.config["res_channels"], self.native_width()
+        ts = [t.detach().float() for t in ts]
+        if Cp == C_:
+            return ts
+        row = lambda t, halves=1: _pad_rows(t, C_, Cp, halves)
+        out = [row(ts[0]), row(ts[1]), _pad_v(ts[2], C_, Cp)] + ts[3:7]
+        for k in range(7, len(ts) - 5, 11):
+            fw, fb, db, dg, dv, rb, rg, rv, sb, sg, sv = ts[k:k + 11]
+            out += [row(fw), row(fb), row(db, 2), row(dg, 2), _pad_v(dv, C_, Cp, 2), row(rb), row(rg), _pad_v(rv, C_, Cp), row(sb), row(sg),
+                    _pad_v(sv, C_, Cp)]
+        fb, fg, fv, w2, b2 = ts[-5:]
+        return out + [row(fb), row(fg), _pad_v(fv, C_, Cp), row(w2.reshape(-1)).reshape(1, -1, 1), b2]
+
     @N.on_device
     def engine(self) -> NativeEngine:
         """Fold + pack the current parameters into the native context (re-done when any parameter changed)."""
@@ -261,10 +313,12 @@ class WaveNet_Speech_Commands(nn.Module):
             raise N.NativeError("audiopure_amd WaveNet needs its parameters on a HIP device (.cuda()); no CPU path")
         key = (dev, tuple((t._version, t.data_ptr()) for t in ts))
         if self._engine is None:
-            self._engine = NativeEngine(self.config, self._precision)
+            Cp = self.native_width()
+            self._engine = NativeEngine(dict(self.config, res_channels=Cp, skip_channels=Cp) if Cp != self.config["res_channels"] else self.config,
+                                        self._precision)
         if self._engine.loaded_key != key:
             with torch.no_grad():
-                blob = torch.cat([t.detach().reshape(-1).float() for t in ts]).contiguous()
+                blob = torch.cat([t.reshape(-1) for t in self._native_tensors(ts)]).contiguous()
                 freq = embedding_frequencies(self.config["diffusion_step_embed_dim_in"]).to(dev).contiguous()
                 self._engine.load(blob, freq)
             self._engine.loaded_key = key

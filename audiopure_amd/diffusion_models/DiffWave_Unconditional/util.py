@@ -64,3 +64,56 @@ def sampling(net, size, diffusion_hyperparams, noise_source=None):
     with torch.no_grad():                                   # x_T = 0 * x + 1 * z_0, then the T links
         return dw._chain(zeros, dw._ddpm_steps(T), 0.0, 1.0, n_draws=T)
 
+
+_HOST_TABLES = {}
+
+
+def _host_table(t):
+    """A schedule table as an fp32 CPU tensor; a table that lives on the device is copied once per version, not once per call
+    (the copy synchronises the host)."""
+    if not t.is_cuda:
+        return t.detach().float()
+    key = (t.data_ptr(), t._version, tuple(t.shape))
+    if _HOST_TABLES.get("key") != key:
+        _HOST_TABLES["key"], _HOST_TABLES["value"] = key, t.detach().cpu().float()
+    return _HOST_TABLES["value"]
+
+
+def training_loss(net, loss_fn, X, diffusion_hyperparams, noise_source=None):
+    """The training loss of epsilon against epsilon_theta (util.py:161-185): steps t_b ~ U{0..T-1} and z ~ N(0, 1) per clip,
+    x_t = sqrt(abar[t]) X + sqrt(1 - abar[t]) z (``ap_affine_noise`` per group of clips sharing a step), epsilon_theta from the
+    HIP library, ``loss_fn(epsilon_theta, z)`` (the caller's torch callable, ``nn.MSELoss()`` in train.py).  ``.backward()`` on
+    the result fills ``.grad`` of every parameter of ``net`` (the last block's res_conv excepted: its output is unused,
+    WaveNet.py:133) and of ``X`` if it requires grad.  fp32 arithmetic only ("f32" / "f32d"); the other modes raise.
+    ``noise_source``: None -- ``torch.randint`` for the steps, ``torch.randn`` on the device for z; ("philox", seed, utt_offset) --
+    z from the library's counter-based stream; (diffusion_steps [B] int, z [B,1,L]) -- both injected (parity tests)."""
+    from .._grad import _require_f32, q_sample_per_clip, step_groups, training_eps
+    from ... import _native as N
+    _require_f32(net, "training_loss")
+    _dh = diffusion_hyperparams
+    T, Alpha_bar = int(_dh["T"]), _host_table(_dh["Alpha_bar"])
+    if X.dim() != 3 or X.shape[1] != 1:
+        raise ValueError(f"training_loss: expected audio of shape [B,1,L], got {tuple(X.shape)}")
+    B, _, L = X.shape
+    dev = X.device
+    src = noise_source
+    if src is not None and not isinstance(src[0], str):
+        steps, z = src
+        steps = torch.as_tensor(steps).reshape(-1)
+        z = torch.as_tensor(z).to(dev).float().reshape(B, 1, L).contiguous()
+    else:
+        steps = torch.randint(T, size=(B, 1, 1)).reshape(-1)                      # util.py:181
+        if src is None:
+            z = torch.randn((B, 1, L), device=dev)
+        else:
+            assert src[0] == "philox"
+            z = torch.empty((B, 1, L), device=dev)
+            N.check(N.lib().ap_philox_normal(N.ptr(z), int(src[1]), 0, int(src[2]) if len(src) > 2 else 0, B, L, N.stream()),
+                    "ap_philox_normal")
+    steps = [int(t) for t in steps.tolist()]
+    if len(steps) != B or min(steps) < 0 or max(steps) >= T:
+        raise ValueError("training_loss: one diffusion step in [0, T) per clip")
+    groups = [((float(torch.sqrt(Alpha_bar[int(t)])), float(torch.sqrt(1 - Alpha_bar[int(t)]))), idx) for t, idx in step_groups(steps)]
+    x_t = q_sample_per_clip(X, z, groups)                                         # util.py:183
+    epsilon_theta = training_eps(net, x_t, steps)                                 # util.py:184
+    return loss_fn(epsilon_theta, z)

@@ -12,9 +12,16 @@ chain fits a memory budget (``SAVE_BUDGET_BYTES``; 288 GB of HBM hold a PGD batc
 (the adjoint's memory/compute trade).
 
 ``J_eps^T v`` runs on the HIP library.  Which forward sweep a link runs, what it keeps and which backward reads that is
-decided in one place, ``_link_plan`` (the table of kernels per arithmetic mode is its docstring).  Gradients with respect
-to the network's parameters are not formed (the attack differentiates with respect to the audio only; parameters
-are frozen at evaluation, ``adaptive_attack_eval.py:98-101``).
+decided in one place, ``_link_plan`` (the table of kernels per arithmetic mode is its docstring).  The attack differentiates
+with respect to the audio only (parameters are frozen at evaluation, ``adaptive_attack_eval.py:98-101``), so the chain forms
+no parameter gradients.
+
+Training does (``DiffWave_Unconditional/util.py:161-185`` ``training_loss``, then ``loss.backward()`` in ``train.py``):
+``EpsGrad.backward(saved, d_eps, param_grads)`` contracts, in the same sweep, every cotangent it forms with the activation
+it belongs to -- ``ap_wgrad_corr`` for the conv weights, ``ap_rowsum`` for the biases, the FiLM vectors, the init conv and
+``final_conv.2``, ``ap_embed_bwd`` for the step-embedding MLP -- into a ``ParamGrads``, whose ``finish()`` takes the folded
+weights' gradients back to ``weight_g`` / ``weight_v`` (``ap_weight_norm_bwd``).  ``training_eps`` is the autograd node over
+(x_t, parameters) that ``util.training_loss`` calls.  fp32 arithmetic only.
 """
 from __future__ import annotations
 
@@ -168,13 +175,13 @@ class EpsGrad:
                 a=pack(w1),                                                           # u -> pre-gate a   (C -> 2C, k=3, dil d)
                 g=pack(w2.t().reshape(C_, C_ + S_, 1, 1)),                            # [RS dh'; dskip] -> dg  (C+S -> C, 1x1)
                 u=pack(w1.flip(3).permute(1, 0, 2, 3)),                               # da -> du   (2C -> C, k=3 flipped, dil d)
-                b1=blocks[n].dilated_conv_layer.conv.bias.detach().float().contiguous()))
+                b1=net.pad_rows(blocks[n].dilated_conv_layer.conv.bias.detach().float(), 2).contiguous()))
         s = float(torch.tensor(math.sqrt(1.0 / NL), dtype=torch.float32))             # WaveNet.py:135
         wf1 = folded(3, 0, S_ * S_).reshape(S_, S_) * s
         self.wf1 = pack(wf1.reshape(S_, S_, 1, 1))                                    # skip_sum -> r (scale folded in)
         self.wf1_t = pack(wf1.t().reshape(S_, S_, 1, 1))                              # dr -> dskip
-        self.bf1 = net.final_conv[0].conv.bias.detach().float().contiguous()
-        self.wf2 = net.final_conv[2].conv.weight.detach().float().reshape(-1).contiguous()
+        self.bf1 = net.pad_rows(net.final_conv[0].conv.bias.detach().float()).contiguous()
+        self.wf2 = net.pad_rows(net.final_conv[2].conv.weight.detach().float().reshape(-1)).contiguous()
         self.w0 = folded(4, 0, C_)
         self.ones = torch.ones(C_, device=dev)
         self.C, self.S, self.NL = C_, S_, NL
@@ -281,9 +288,13 @@ class EpsGrad:
         N.check(lib.ap_final_affine(ctx, N.ptr(skip), None, N.ptr(eps), None, 0.0, 0.0, 0.0, None, 0, 0, 0, B, L, st), "ap_final_affine")
         return eps, saved
 
-    def backward(self, saved, d_eps: torch.Tensor) -> torch.Tensor:
+    def backward(self, saved, d_eps: torch.Tensor, param_grads: "Optional[ParamGrads]" = None) -> torch.Tensor:
         """J_eps(x, t)^T d_eps for the evaluation ``saved`` came from; the per-layer form follows what the save holds and the flags
-        as they are now (_backward_form)."""
+        as they are now (_backward_form).  ``param_grads``: also add this evaluation's parameter gradients to it (fp32 mode; the
+        object must have been told the evaluation's input and step: ``ParamGrads.at``); None: the same launches as ever."""
+        pg = param_grads
+        if pg is not None:
+            _require_f32(self.net, "EpsGrad.backward(param_grads=...)")
         eng = self._prepare()
         lib, ctx = eng.lib, eng.ctx
         hs, skip, part, pre, fac = saved
@@ -296,8 +307,16 @@ class EpsGrad:
         self._conv(lib, skip, self.wf1, self.bf1, None, r, B, S_, L, S_, 1, 0, 1)
         dr = torch.empty_like(r)
         N.check(lib.ap_relu_outer_bwd(N.ptr(r), N.ptr(self.wf2), N.ptr(d_eps), N.ptr(dr), B, S_, L, st), "ap_relu_outer_bwd")
+        if pg is not None:                                        # final_conv (WaveNet.py:160-162), before r is reused
+            pg.begin(self, eng, B, L, dev)
+            pg.rowsum(r, d_eps, r, pg.f2_w, B, S_, L, bcast=True)            # d f2.weight[s] = sum relu(r)[s] d_eps
+            pg.rowsum(d_eps, None, None, pg.f2_b, B, 1, L)
+            pg.rowsum(dr, None, None, pg.f1_b, B, S_, L)
+            pg.corr(dr, skip, None, pg.f1_w, B, S_, S_, L, 1, 1, _WG_PLAIN, math.sqrt(1.0 / NL))   # d f1.weight = sum dr (x) (s skip)
         dskip = r                                                 # reuse
         self._conv(lib, dr, self.wf1_t, None, None, dskip, B, S_, L, S_, 1, 0, 1)
+        if pg is not None:
+            pg.rowsum(dskip, None, None, pg.skip_b, B, S_, L)     # d skip.bias: the same for every layer
         dh = torch.zeros((B, C_, L), device=dev)                  # the last block's h' output is not used (WaveNet.py:133)
         form = _backward_form(self.net._precision, pre is not None, fac is not None, self.fused_bf16,
                               lib.ap_resblock_bwd_available(ctx, B, L), lib.ap_resblock_bwd_bf16_available(ctx, B, L))
@@ -320,6 +339,8 @@ class EpsGrad:
                                                      dy.data_ptr(), N.ptr(dh2), B, L, st), "ap_resblock_bwd_bf16")
             for n in range(NL - 1, -1, -1):
                 layer(n, dh, dh2)
+                if pg is not None:                                # (fp32 form only: dy [B][2C][L] fp32, the gate from pre_gate[n])
+                    pg.layer(n, self.layers[n]["d"], dy, hs[n], part[n * C_:(n + 1) * C_], dh, dskip, pre[n], dh2, B, L)
                 dh, dh2 = dh2, dh
         else:
             z = torch.empty((B, C_ + S_, L), device=dev)         # [RS dh' ; dskip], dskip is the same for every block
@@ -342,10 +363,242 @@ class EpsGrad:
                             "ap_affine_nchw")
                     self._conv(lib, u, lay["a"], lay["b1"], None, a, B, C_, L, 2 * C_, 3, d, d)
                 N.check(lib.ap_gate_bwd(N.ptr(a if pre is None else pre[n]), N.ptr(dg), N.ptr(da), B, C_, L, st), "ap_gate_bwd")
+                if pg is not None:                                # dh still holds dh'; the conv below overwrites it with dh_in
+                    pg.layer(n, d, da, hs[n], part[n * C_:(n + 1) * C_], dh, dskip, a if pre is None else pre[n], None, B, L)
                 self._conv(lib, da, lay["u"], None, t1, dh, B, 2 * C_, L, C_, 3, d, d)
+                if pg is not None:
+                    pg.film(n, dh, B, L)
         dx = torch.empty((B, 1, L), device=dev)
         N.check(lib.ap_init_conv_bwd(N.ptr(hs[0]), N.ptr(self.w0), N.ptr(dh), N.ptr(dx), B, C_, L, st), "ap_init_conv_bwd")
+        if pg is not None:
+            pg.end(hs[0], dh, part[NL * C_:], B, L)
         return dx
+
+
+_MODE_NAMES = {N.AP_PREC_F32: "f32", N.AP_PREC_BF16: "bf16", N.AP_PREC_F32_SPLIT: "f32s", N.AP_PREC_BF16_STORE: "bf16s"}
+_WG_PLAIN, _WG_FILM, _WG_GATE = 0, 1, 2     # ap_wgrad_corr's staging modes
+
+
+def _require_f32(net, who: str) -> None:
+    """Parameter gradients exist in fp32 arithmetic only: refuse the other modes by name, before any launch."""
+    if net._precision != N.AP_PREC_F32:
+        raise N.NativeError(f"{who}: parameter gradients are built for set_precision('f32') / ('f32d') only; this network is in "
+                            f"{_MODE_NAMES.get(net._precision, net._precision)!r} mode")
+
+
+class ParamGrads:
+    """fp32 device buffers shaped like the folded weights and the biases of one WaveNet_Speech_Commands, which
+    ``EpsGrad.backward(saved, d_eps, param_grads)`` adds one evaluation's gradients to (always ``accumulate = 1`` onto zeros, so
+    sub-batches add up in call order), and ``finish()``: the gradients of the parameters themselves, weight-norm unfolded."""
+
+    def __init__(self, net):
+        _require_f32(net, "ParamGrads")
+        self.net = net
+        cfg = net.config
+        self.width = cfg["res_channels"]                                         # the parameters' own width; the buffers have the native one
+        C_ = S_ = net.native_width()                                             # (the library is built for skip = res channels)
+        NL = cfg["num_res_layers"]
+        Ein, Emid, Eout = (cfg["diffusion_step_embed_dim_in"], cfg["diffusion_step_embed_dim_mid"], cfg["diffusion_step_embed_dim_out"])
+        self.C, self.S, self.NL = C_, S_, NL
+        dev = next(net.parameters()).device
+        z = lambda *shape: torch.zeros(shape, device=dev, dtype=torch.float32)
+        self.w0, self.b0 = z(C_), z(C_)                                          # init conv (folded [C][1])
+        self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b = z(Emid, Ein), z(Emid), z(Eout, Emid), z(Eout)
+        self.fct_w, self.fct_b = z(NL, C_, Eout), z(NL, C_)
+        self.w1, self.b1 = z(NL, 2 * C_, C_, 3), z(NL, 2 * C_)                   # dilated conv (folded)
+        self.res_w, self.res_b = z(NL, C_, C_), z(NL, C_)                        # (the last block's stay unused: WaveNet.py:133)
+        self.skip_w, self.skip_b = z(NL, S_, C_), z(S_)                          # skip.bias: one sum serves every layer
+        self.f1_w, self.f1_b, self.f2_w, self.f2_b = z(S_, S_), z(S_), z(S_), z(1)
+        self.dpart = torch.zeros((NL, C_), device=dev, dtype=torch.float64)      # FiLM cotangents of the evaluation in flight (fp64: ap_embed_bwd)
+        self._ws = self._scratch = self._x = self._step = None
+
+    def at(self, x: torch.Tensor, step: float) -> "ParamGrads":
+        """Name the evaluation the next ``EpsGrad.backward`` call belongs to: its input x [B,1,L] (the init conv's weight gradient
+        needs it) and its step (the embedding MLP is recomputed from it)."""
+        self._x, self._step = x.detach().float().contiguous(), float(step)
+        return self
+
+    # ---- called by EpsGrad.backward, in sweep order ---------------------------------------------------------
+    def begin(self, grad, eng, B, L, dev):
+        if self._x is None or tuple(self._x.shape) != (B, 1, L):
+            raise N.NativeError("ParamGrads: call at(x, step) with this evaluation's input before EpsGrad.backward")
+        self.lib, self.ctx = eng.lib, eng.ctx
+        if self._scratch is None:
+            self._scratch = torch.empty(self.lib.ap_embed_bwd_scratch_elems(self.ctx), device=dev, dtype=torch.float32)
+
+    def corr(self, P, Q, film, G, B, M, Nn, L, taps, dil, mode, scale):
+        need = self.lib.ap_wgrad_workspace_bytes(B, M, Nn, L, taps)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, device=P.device, dtype=torch.uint8)
+        N.check(self.lib.ap_wgrad_corr(N.ptr(P), N.ptr(Q), N.ptr(film), N.ptr(G), self._ws.data_ptr(), self._ws.numel(), B, M, Nn, L,
+                                       taps, dil, mode, float(scale), 1, N.stream()), "ap_wgrad_corr")
+
+    def rowsum(self, A, W, R, out, B, M, L, bcast=False, scale=1.0, accumulate=1):
+        N.check(self.lib.ap_rowsum(N.ptr(A), N.ptr(W), N.ptr(R), N.ptr(out), B, M, L, 1 if bcast else 0, float(scale), accumulate,
+                                   N.stream()), "ap_rowsum")
+
+    def layer(self, n, d, dy, h_in, film, dh_out, dskip, y, du, B, L):
+        """Block n (WaveNet.py:75-97): dy = d loss / d (DilConv(u) + b), u = h_in + film; y: its pre-gate activations; dh_out =
+        d loss / d h'; du = d loss / d u (None: handed to film() later)."""
+        C_, S_ = self.C, self.S
+        self.corr(dy, h_in, film, self.w1[n], B, 2 * C_, C_, L, 3, d, _WG_FILM, 1.0)
+        self.rowsum(dy, None, None, self.b1[n], B, 2 * C_, L)
+        if n + 1 < self.NL:                                       # the last block's h' is unused: no gradient, no launch
+            self.corr(dh_out, y, None, self.res_w[n], B, C_, C_, L, 1, 1, _WG_GATE, _RS)
+            self.rowsum(dh_out, None, None, self.res_b[n], B, C_, L, scale=_RS)
+        self.corr(dskip, y, None, self.skip_w[n], B, S_, C_, L, 1, 1, _WG_GATE, 1.0)
+        if du is not None:
+            self.film(n, du, B, L)
+
+    def film(self, n, du, B, L):
+        N.check(self.lib.ap_rowsum_f64(N.ptr(du), self.dpart[n].data_ptr(), B, self.C, L, 0, N.stream()), "ap_rowsum_f64")   # dpart_n = sum du_n (this evaluation's alone)
+
+    def end(self, h0, dh0, emb, B, L):
+        self.rowsum(dh0, self._x, h0, self.w0, B, self.C, L, bcast=True)         # dw0[c] = sum dh0[c] [h0[c] > 0] x
+        self.rowsum(dh0, None, h0, self.b0, B, self.C, L)
+        N.check(self.lib.ap_embed_bwd(self.ctx, self._step, self.dpart.data_ptr(), N.ptr(emb), N.ptr(self.fct_w), N.ptr(self.fct_b),
+                                      N.ptr(self.fc1_w), N.ptr(self.fc1_b), N.ptr(self.fc2_w), N.ptr(self.fc2_b), N.ptr(self._scratch), 1,
+                                      N.stream()), "ap_embed_bwd")
+        self._x = self._step = None
+
+    # ---- after the sweep(s) ---------------------------------------------------------------------------
+    def _unfold(self, dW, conv):
+        """(d weight_g, d weight_v) of a weight-normed conv from the gradient of its folded weight."""
+        g, v = conv.weight_g.detach(), conv.weight_v.detach()
+        dg, dv = torch.empty_like(g), torch.empty_like(v)
+        rows = v.shape[0]
+        N.check(N.lib().ap_weight_norm_bwd(N.ptr(dW), N.ptr(v), N.ptr(g), N.ptr(dg), N.ptr(dv), rows, v.numel() // rows, N.stream()),
+                "ap_weight_norm_bwd")
+        return dg, dv
+
+    def finish(self) -> list:
+        """Gradients in the order of ``net._blob_tensors()`` (the state dict's); None for the last block's res_conv, as the
+        reference's autograd leaves them."""
+        net, NL, W, Cp = self.net, self.NL, self.width, self.C
+        rows = lambda t: t[:W]                                                   # the real channels of a native-width buffer
+        sq = lambda t: t[:W, :W].contiguous() if W != Cp else t
+        halves = lambda t: torch.cat([t[:W], t[Cp:Cp + W]], 0)[:, :W].contiguous() if W != Cp else t   # tanh rows, sigmoid rows
+        ic, f0 = net.init_conv[0].conv, net.final_conv[0].conv
+        out = [rows(self.b0), *self._unfold(rows(self.w0), ic), self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b]
+        for n, b in enumerate(net.residual_layer.residual_blocks):
+            b1 = torch.cat([self.b1[n][:W], self.b1[n][Cp:Cp + W]]) if W != Cp else self.b1[n]
+            out += [rows(self.fct_w[n]), rows(self.fct_b[n]), b1, *self._unfold(halves(self.w1[n]), b.dilated_conv_layer.conv)]
+            out += [rows(self.res_b[n]), *self._unfold(sq(self.res_w[n]), b.res_conv)] if n + 1 < NL else [None, None, None]
+            out += [rows(self.skip_b).clone(), *self._unfold(sq(self.skip_w[n]), b.skip_conv)]
+        out += [rows(self.f1_b), *self._unfold(sq(self.f1_w), f0), rows(self.f2_w).reshape(1, -1, 1), self.f2_b]
+        return out
+
+
+def step_groups(steps) -> list:
+    """Clips grouped by distinct step, as WaveNet_Speech_Commands.forward groups them: [(step, [clip indices ascending])], the
+    groups in the order of their first clip."""
+    groups = {}
+    for i, t in enumerate(steps):
+        groups.setdefault(float(t), []).append(i)
+    return sorted(groups.items(), key=lambda kv: kv[1][0])
+
+
+def plan_sub_batches(steps, bytes_of, budget) -> list:
+    """The eps evaluations of one training step: [(step, [clip indices])].  Every group of ``step_groups`` is cut into runs of the
+    largest clip count k whose save fits (``bytes_of(k) <= budget``, ``bytes_of`` non-decreasing; one clip always goes), in
+    ascending clip order -- so every clip is evaluated exactly once whatever the budget.  Pure host logic."""
+    out = []
+    for t, idx in step_groups(steps):
+        lo, hi = 1, len(idx)                                     # largest k in [1, len] that fits (k = 1 regardless)
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if bytes_of(mid) <= budget else (lo, mid - 1)
+        out += [(t, idx[s:s + lo]) for s in range(0, len(idx), lo)]
+    return out
+
+
+class _TrainEpsFn(torch.autograd.Function):
+    """eps_theta(x_t, steps) with per-clip steps, differentiable in x_t and in the network's parameters (``params``: exactly
+    ``net._blob_tensors()``, handed over so that autograd routes their gradients).  One saving forward per sub-batch of
+    ``plan_sub_batches``; a sub-batch's save is kept for the backward pass while the total fits the budget (``_save_level``, as a
+    chain's links) and recomputed otherwise; the backward pass walks the sub-batches in the same order into one ParamGrads."""
+
+    @staticmethod
+    def forward(ctx, x_t, grad, steps, *params):
+        x = x_t.detach().float().contiguous()
+        eps = torch.empty_like(x)
+        budget = _chain_budget(x.device)
+        batches = plan_sub_batches(steps, lambda k: grad.saved_bytes(x[:k], True), budget)
+        saves, held, once = [], 0, 0
+        with torch.no_grad():
+            for t, idx in batches:
+                sel = torch.tensor(idx, device=x.device)
+                xs = x[sel]
+                full, first = grad.saved_bytes(xs, True, split=True)
+                e, saved = grad.forward_save(xs, t)
+                level, held, once = _save_level(held, max(once, first), full, full, budget)
+                saves.append(saved if level is not None else None)
+                eps[sel] = e
+                del saved
+        ctx.grad, ctx.batches, ctx.saves, ctx.x = grad, batches, saves, x
+        return eps
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, x = ctx.grad, ctx.x
+        g = g.detach().float().contiguous()
+        dx = torch.empty_like(x)
+        with torch.no_grad():
+            pg = ParamGrads(grad.net)
+            for k, (t, idx) in enumerate(ctx.batches):
+                sel = torch.tensor(idx, device=x.device)
+                xs = x[sel]
+                saved, ctx.saves[k] = ctx.saves[k], None
+                if saved is None:                                # over budget in the forward pass: the adjoint's trade
+                    _, saved = grad.forward_save(xs, t)
+                dx[sel] = grad.backward(saved, g[sel], pg.at(xs, t))
+                del saved
+            grads = pg.finish()
+        return (dx, None, None, *grads)
+
+
+class _QSampleFn(torch.autograd.Function):
+    """x_t = sqrt(abar[t_b]) X_b + sqrt(1 - abar[t_b]) z_b per clip (util.py:183), ``ap_affine_noise`` per group of clips sharing a step."""
+
+    @staticmethod
+    def forward(ctx, X, z, groups):
+        x = X.detach().float().contiguous()
+        B, _, L = x.shape
+        out = torch.empty_like(x)
+        with torch.no_grad():
+            for (ca, cs), idx in groups:
+                sel = torch.tensor(idx, device=x.device)
+                xs, zs = x[sel], z[sel]
+                o = torch.empty_like(xs)
+                N.check(N.lib().ap_affine_noise(N.ptr(xs), N.ptr(o), float(ca), float(cs), N.ptr(zs), 0, 0, 0, len(idx), L, N.stream()),
+                        "ap_affine_noise")
+                out[sel] = o
+        ctx.groups = groups
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.detach().float().contiguous()
+        dX = torch.empty_like(g)
+        with torch.no_grad():
+            for (ca, _), idx in ctx.groups:
+                sel = torch.tensor(idx, device=g.device)
+                dX[sel] = _axpby(g[sel], None, ca, 0.0)
+        return dX, None, None
+
+
+def q_sample_per_clip(X, z, groups):
+    """``groups``: [((sqrt(abar_t), sqrt(1 - abar_t)), [clip indices])]."""
+    return _QSampleFn.apply(X, z, groups)
+
+
+def training_eps(net, x_t, steps):
+    """eps_theta(x_t, steps) as an autograd node over x_t and every parameter of ``net`` (``steps``: one value per clip)."""
+    _require_f32(net, "training_eps")
+    if not torch.is_grad_enabled():                              # an evaluation of the loss only: the plain forward, nothing kept
+        return net((x_t, torch.tensor([float(t) for t in steps])))
+    return _TrainEpsFn.apply(x_t, _eps_grad_of(net), tuple(float(t) for t in steps), *net._blob_tensors())
 
 
 def _axpby(x, y, a, b):

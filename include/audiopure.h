@@ -257,9 +257,9 @@ int ap_resblock_fwd_save(ap_ctx *ctx, int layer, const float *h_in, const float 
  *   dy = gate'(pre_gate) . ([W_res sqrt(1/2); W_skip]^T [dh_out; dskip])       -> dy_scratch [B][2C][L]
  *   dh_in = sqrt(1/2) dh_out + DilConv^T(dy)                                    (F(2,3) form of the transposed dilated conv)
  * dh_out = d loss / d h' [B][C][L] (zeros for the net's last layer, whose h' is unused), dskip = d loss / d skip_n [B][S][L] (the
- * same tensor for every layer: skip is their sum), pre_gate: what ap_resblock_fwd_save kept for this layer.  Parameters are
- * frozen (no weight gradients).  AP_PREC_F32, res = skip = 256 channels; ap_resblock_bwd_available returns 1 exactly where
- * ap_resblock_bwd serves (B, L) in this context. */
+ * same tensor for every layer: skip is their sum), pre_gate: what ap_resblock_fwd_save kept for this layer.  The parameters' own
+ * gradients are formed from the same cotangents by ap_wgrad_corr / ap_rowsum (below).  AP_PREC_F32, res = skip = 256 channels;
+ * ap_resblock_bwd_available returns 1 exactly where ap_resblock_bwd serves (B, L) in this context. */
 int ap_resblock_bwd(ap_ctx *ctx, int layer, const float *dh_out, const float *dskip, const float *pre_gate, float *dy_scratch,
                     float *dh_in, int B, int L, void *stream);
 /* The backward kernels read their own weight images (fp32: 94 MB, bf16: 47 MB at the shipped shape).  ap_ctx_prepare_backward
@@ -573,6 +573,44 @@ int ap_melspec_db_bwd(const float *x, const float *dout, float *dx, float *scrat
 int ap_m5_bwd(ap_m5 *m, const float *x, const float *dlogprobs, float *dx, int B, int L, void *stream);
 /* WaveNet.py:147,168 backward: dx[b][t] = sum_c [h0 > 0] w0[c] dh0[b][c][t] */
 int ap_init_conv_bwd(const float *h0, const float *w0, const float *dh0, float *dx, int B, int C, int L, void *stream);
+
+/* ---- parameter gradients of the eps-network (the reference trains it: DiffWave_Unconditional/util.py:161-185 `training_loss`,
+ * loss.backward() and Adam in train.py / train_qkws.py).  The input-gradient sweep above forms every cotangent; these contract a
+ * cotangent with an activation over (clip, time).  Every sum has a fixed order (no atomics): two runs give the same bits. ---- */
+/* Weight gradient of a k = 1 or k = 3 dilated, zero-padded Conv1d (WaveNet.py:26-27 dilated conv :87, res_conv :93, skip_conv :95,
+ * final_conv.0 :160), on the exact-fp32 matrix instruction:
+ *   G[m][n][k] (+)= p_scale * sum_b sum_t P[b][m][t] * Q~[b][n][t + (k - taps/2) dil],   terms with the Q index outside [0, L) are 0.
+ * P [B][M][L] is the cotangent of the conv's output, G [M][N][taps] has the layout of the conv's weight.  Q~ by `mode`:
+ *   0  Q [B][N][L] as given;
+ *   1  Q + film[n] inside [0, L) (the conv pads u = h + part_t with zeros, so padded samples stay 0; WaveNet.py:84,87);
+ *   2  tanh(Q[n]) * sigmoid(Q[n + N]) from pre-gate rows Q [B][2N][L] (WaveNet.py:90).
+ * M, N: multiples of 32; taps 1 or 3 (dil ignored for taps = 1); L >= 1.  A tap with |offset| >= L meets no sample: it is skipped and
+ * contributes exact zeros.  K = B L is split over workgroups; the partial sums go to `workspace` (ap_wgrad_workspace_bytes(B, M, N, L,
+ * taps) bytes, caller-owned: the launch allocates nothing) and a second kernel adds them in slice order; accumulate != 0 adds to G. */
+size_t ap_wgrad_workspace_bytes(int B, int M, int N, int L, int taps);
+int ap_wgrad_corr(const float *P, const float *Q, const float *film, float *G, void *workspace, size_t ws_bytes, int B, int M, int N,
+                  int L, int taps, int dil, int mode, float p_scale, int accumulate, void *stream);
+/* out[m] (+)= scale * sum_b sum_t A[b][m][t] * w, A [B][M][L]; w = W's element (W [B][M][L], or the broadcast row W [B][1][L] with
+ * w_broadcast != 0; 1 if W is NULL), taken only where R[b][m][t] > 0 if R [B][M][L] is given.  Every conv bias (the sum of its output's
+ * cotangent), the init conv's dw0 / db0 (mask h0 > 0, times x; WaveNet.py:147,168) and final_conv.2's weight (sum relu(r) d_eps;
+ * WaveNet.py:161-162).  (The FiLM cotangents are the same plain sum, handed out as fp64: ap_rowsum_f64.) */
+int ap_rowsum(const float *A, const float *W, const float *R, float *out, int B, int M, int L, int w_broadcast, float scale,
+              int accumulate, void *stream);
+/* The plain sum (w = 1, scale 1) handed out as fp64: the FiLM cotangents dpart_n = sum du_n (WaveNet.py:82-84), which ap_embed_bwd
+ * takes through long cancelling sums.  (ap_rowsum itself sums in fp64 too and rounds once on the way out.) */
+int ap_rowsum_f64(const float *A, double *out, int B, int M, int L, int accumulate, void *stream);
+/* Backward of ap_embed (util.py:68-93; WaveNet.py:82-83,124-126) with the context's loaded weights: from dpart [num_res_layers][C] (fp64:
+ * ap_rowsum_f64; everything between it and the results is summed in fp64, so sub-batches add up to what one batch gives) and the
+ * embedding ap_embed left behind its FiLM vectors (emb [embed_dim_out]):  d fc_t_n.weight = dpart_n (x) emb [NL][C][Eout], d fc_t_n.bias
+ * [NL][C], then through swish(fc_t2(swish(fc_t1(.)))) (recomputed from `step`) the gradients of fc_t2 and fc_t1, each (+)= into buffers
+ * shaped like the parameter.  scratch: ap_embed_bwd_scratch_elems(ctx) floats, 8-byte aligned. */
+size_t ap_embed_bwd_scratch_elems(const ap_ctx *ctx);
+int ap_embed_bwd(ap_ctx *ctx, float step, const double *dpart, const float *emb, float *d_fct_w, float *d_fct_b, float *d_fc1_w,
+                 float *d_fc1_b, float *d_fc2_w, float *d_fc2_b, float *scratch, int accumulate, void *stream);
+/* Gradient of the weight-norm fold W[o] = g[o] v[o] / ||v[o]|| (WaveNet.py:23-34, nn.utils.weight_norm dim = 0): from dW [rows][cols],
+ *   dg[o] = (dW[o] . v[o]) / ||v[o]||,   dv[o] = (g[o] / ||v[o]||) (dW[o] - v[o] (dW[o] . v[o]) / ||v[o]||^2).
+ * cols = 1 (the init conv): dv is exactly 0. */
+int ap_weight_norm_bwd(const float *dW, const float *v, const float *g, float *dg, float *dv, int rows, int cols, void *stream);
 
 #ifdef __cplusplus
 }
