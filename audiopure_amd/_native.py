@@ -151,6 +151,10 @@ SIGNATURES = {
     "ap_rowsum_f64": (_i, [_fp, _vp, _i, _i, _i, _i, _vp]),
     "ap_embed_bwd_scratch_elems": (_sz, [_vp]),
     "ap_embed_bwd": (_i, [_vp, _f, _vp] + [_fp] * 8 + [_i, _vp]),
+    "ap_m5_param_elems": (_sz, [_vp]),
+    "ap_m5_train_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "ap_m5_train_fwd": (_i, [_vp, _fp, _fp, _fp, _fp, _f, _vp, _sz, _i, _i, _i, _vp]),
+    "ap_m5_train_bwd": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _i, _i, _vp]),
     "ap_weight_norm_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
 }
 

@@ -730,7 +730,7 @@ extern "C" int ap_m5_create(int n_output, int n_channel, int first_kernel, int s
   }
   ap_m5 *m = new (std::nothrow) ap_m5();
   if (!m) { set_error("out of host memory"); return -12; }
-  m->n_output = n_output; m->n_channel = n_channel; m->k1 = first_kernel; m->stride = stride;
+  m->n_output = n_output; m->n_channel = n_channel; m->k1 = first_kernel; m->stride = stride; m->eps = bn_eps;
   int ci[4] = {1, n_channel, n_channel, 2 * n_channel};
   int co[4] = {n_channel, n_channel, 2 * n_channel, 2 * n_channel};
   int k[4] = {first_kernel, 3, 3, 3};
@@ -766,4 +766,27 @@ extern "C" int ap_m5_bwd(ap_m5 *m, const float *x, const float *dlogprobs, float
 extern "C" int ap_m5_fwd(ap_m5 *m, const float *x, float *logprobs, int B, int L, void *stream) {
   if (!m || !x || !logprobs || B < 1) { set_error("ap_m5_fwd: bad argument"); return -22; }
   return launch_m5(m, x, logprobs, B, L, (hipStream_t)stream);
+}
+
+// ---- M5 in train mode (ap_m5_train.hip) -----------------------------------------------------------
+extern "C" size_t ap_m5_param_elems(const ap_m5 *m) {
+  if (!m) return 0;
+  return ap_m5_blob_elems(m->n_output, m->n_channel, m->k1) - 2 * (size_t)6 * m->n_channel;   // the blob less 4 x (running_mean, running_var)
+}
+
+extern "C" size_t ap_m5_train_workspace_bytes(const ap_m5 *m, int B, int L) {
+  if (!m || B < 1) { set_error("ap_m5_train_workspace_bytes: bad argument"); return 0; }
+  return m5_train_workspace_bytes(m, B, L);
+}
+
+extern "C" int ap_m5_train_fwd(ap_m5 *m, const float *blob, const float *x, float *logprobs, float *new_running, float momentum,
+                               void *workspace, size_t ws_bytes, int keep, int B, int L, void *stream) {
+  if (!m || !blob || !x || !logprobs || !new_running || !workspace || B < 1) { set_error("ap_m5_train_fwd: bad argument"); return -22; }
+  return launch_m5_train_fwd(m, blob, x, logprobs, new_running, momentum, workspace, ws_bytes, keep, B, L, (hipStream_t)stream);
+}
+
+extern "C" int ap_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float *dlogprobs, float *grads, float *dx,
+                               void *workspace, size_t ws_bytes, int B, int L, void *stream) {
+  if (!m || !blob || !x || !dlogprobs || !grads || !workspace || B < 1) { set_error("ap_m5_train_bwd: bad argument"); return -22; }
+  return launch_m5_train_bwd(m, blob, x, dlogprobs, grads, dx, workspace, ws_bytes, B, L, (hipStream_t)stream);
 }

@@ -154,6 +154,7 @@ inline int check_block_args(const char *who, const ap_ctx *ctx, bool ptrs, int l
 
 struct ap_m5 {
   int n_output, n_channel, k1, stride;
+  float eps;              // BatchNorm eps as given to ap_m5_create (the train-mode launchers read it; the eval images have it folded in)
   float *slab;
   float *w[4], *b[4];
   float *fcw, *fcb;
@@ -215,4 +216,10 @@ int prepare_bwd_bf16(ap_ctx *ctx, hipStream_t st);
 int launch_m5(ap_m5 *m, const float *x, float *logprobs, int B, int L, hipStream_t st);
 int launch_m5_bwd(ap_m5 *m, const float *x, const float *dlogp, float *dx, int B, int L, hipStream_t st);
 int launch_m5_fold(ap_m5 *m, const float *blob, float bn_eps, hipStream_t st);
+// ap_m5_train.hip: train-mode M5 (batch-statistics BatchNorm), forward and the parameter / input gradients
+size_t m5_train_workspace_bytes(const ap_m5 *m, int B, int L);   // 0 with the error text set where the shape is refused
+int launch_m5_train_fwd(ap_m5 *m, const float *blob, const float *x, float *logprobs, float *new_running, float momentum, void *ws,
+                        size_t ws_bytes, int keep, int B, int L, hipStream_t st);
+int launch_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float *dlogp, float *grads, float *dx, void *ws, size_t ws_bytes,
+                        int B, int L, hipStream_t st);
 }  // namespace ap

@@ -612,6 +612,29 @@ int ap_embed_bwd(ap_ctx *ctx, float step, const double *dpart, const float *emb,
  * cols = 1 (the init conv): dv is exactly 0. */
 int ap_weight_norm_bwd(const float *dW, const float *v, const float *g, float *dg, float *dv, int rows, int cols, void *stream);
 
+/* ---- M5 in train mode: batch-statistics BatchNorm, parameter gradients (the reference trains the classifier:
+ * audio_models/M5/train.py:86-103 `model.train(); loss = F.nll_loss(model(data), target); loss.backward()`, M5Net.py:21-38 with
+ * nn.BatchNorm1d in training mode).  Stage i = 1..4: z = conv_i(a_{i-1}) + b_i; per channel over all n = B P_i positions the mean and
+ * the BIASED variance; y = gamma (z - mean) / sqrt(var + eps) + beta; a_i = maxpool4(relu(y)) -- max and argmax on y, after the
+ * affine, so a negative gamma is served; then the mean over time, fc1, log_softmax.  The handle supplies geometry and eps only: `blob`
+ * is the LIVE parameter blob in ap_m5_create's order, read at every call; the folded images of the handle are never read.
+ * Activations live in the caller's workspace (ap_m5_train_workspace_bytes; a launch allocates nothing), so there is no LDS ceiling on
+ * L as in ap_m5_fwd / ap_m5_bwd.  -22 before any launch: L too short for four stages, n <= 1 values per channel, workspace too small.
+ * No floating-point atomics: every sum over the batch runs in a fixed number of slices (64, whatever the card), each summed in a fixed
+ * order, and the slices are added in fp64 and rounded once -- two runs give the same bits. */
+/* elements of the gradient blob: per stage conv.weight, conv.bias, bn.weight, bn.bias, then fc1.weight, fc1.bias */
+size_t ap_m5_param_elems(const ap_m5 *m);
+size_t ap_m5_train_workspace_bytes(const ap_m5 *m, int B, int L);   /* 0 (error text set) where the shape is refused */
+/* x [B][1][L] -> logprobs [B][n_output]; new_running [2 sum(co)]: the four stages' new running means, then their new running variances
+ * ((1 - momentum) old + momentum batch value, the variance UNBIASED, n / (n - 1); torch's momentum=None is the host's momentum =
+ * 1 / num_batches_tracked).  keep != 0 leaves in the workspace what ap_m5_train_bwd reads; keep = 0 is the no_grad form. */
+int ap_m5_train_fwd(ap_m5 *m, const float *blob, const float *x, float *logprobs, float *new_running, float momentum, void *workspace,
+                    size_t ws_bytes, int keep, int B, int L, void *stream);
+/* After ap_m5_train_fwd(keep != 0) on the same blob, x and workspace: dlogprobs [B][n_output] -> grads [ap_m5_param_elems] (written,
+ * not accumulated) and, if dx is not NULL, dx [B][1][L]. */
+int ap_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float *dlogprobs, float *grads, float *dx, void *workspace,
+                    size_t ws_bytes, int B, int L, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
