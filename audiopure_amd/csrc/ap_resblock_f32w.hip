@@ -63,8 +63,13 @@ constexpr int DIET_PK_ = 32;             // 16-byte forms: output transform and 
 constexpr int DIET_ZERO_ = 128;          // m1, m3, m4 are not zeroed: chunk 0, peeled, starts them from the instruction's constant 0
 // (with chunk 0 peeled the allocator also stops giving three product tiles other registers in the last chunk than in the chunk loop,
 // which mask 22 pays per tile with 32 v_accvgpr_mov, 80 reads and 80 writes in the last chunk's MFMA gaps: docs/HISTORY.md I.13)
+// MFMAs through the chunk turn (the 16-byte forms; the A/B: profiles/f32w_seam_ab.txt, the budget: profiles/f32w_seam_gap_budget.txt):
+constexpr int DIET_SEAM_ = 1024;         // the chunk's barrier in its last unit, the next chunk's first fragment behind it; X requested in unit 13's gaps
+// (Bit 512, every B fragment pinned a unit ahead of its use, measured 0.04 .. 0.24 % slower in all six cells -- a read one MFMA ahead
+// is already free -- and bit 2048, the staging on channel pairs as 8 v_pk_fma_f32 + 8 v_pk_add_f32 without selects, gained 0.01 ..
+// 0.20 % and stayed inside mask 182's band; neither is in this source: docs/HISTORY.md I.14.)
 #ifndef AP_F32W_DIET
-#define AP_F32W_DIET 182
+#define AP_F32W_DIET 1206
 #endif
 // the 4-byte epilogue form (ragged clip lengths) holds 64 residual values across GEMM2 and has no registers to spare: no item
 constexpr int DIET4_ = 0;
@@ -133,6 +138,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   constexpr bool ROWS = Q16 && !NOH && (DIET & DIET_ROWS_) != 0;                        // every 16-byte form that writes h'
   constexpr bool PK = Q16 && (DIET & DIET_PK_) != 0;
   constexpr bool ZERO = Q16 && (DIET & DIET_ZERO_) != 0;
+  constexpr bool SEAM = Q16 && (DIET & DIET_SEAM_) != 0;
+  static_assert(!SEAM || (CARRY && ZERO), "DIET_SEAM_ is written for the peeled first and last chunk");
   // LDS map (floats): X sub-buffers 0, 1 | g image | Q16: output patches | CONST: b1, b2, part_t
   constexpr int COFF_ = Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_;
   __shared__ __attribute__((aligned(16))) float lds[COFF_ + (CONST ? NCONST_ : 0)];
@@ -276,6 +283,15 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #pragma unroll 1
   for (int tile = t_first; tile < t_end; tile += t_step) {
     f32x16 acc[4][4];                                            // [product][row tile]; the dilated conv's bias rides on m2 (in both outputs)
+    const float *xfrag = lds + j * XS_ + 4 * hh;
+    f32x4 bqc[2];                                                // SEAM: the B fragments, carried from chunk to chunk
+    if constexpr (SEAM) {
+      // the first fragment is on its way while the bias init below reads LDS and writes its 64 accumulators
+      store_x(lds);
+      __syncthreads();
+      bqc[0] = *reinterpret_cast<const f32x4 *>(xfrag);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int rt = 0; rt < 4; rt++) {
       const int obase = (rt & 1) * C + 64 * wave + 32 * (rt >> 1);
@@ -292,26 +308,44 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
         for (int r = 0; r < 16; r++) acc[0][rt][r] = acc[2][rt][r] = acc[3][rt][r] = 0.f;
       }
     }
-    store_x(lds);
-    __syncthreads();
+    if constexpr (!SEAM) {
+      store_x(lds);
+      __syncthreads();
+    }
 
     // ---- GEMM1: 8 chunks x 4 k-groups x 4 products; a unit = 16 MFMAs on one B fragment.  Chunk c + 1 is requested at chunk c's top and
     // staged in its unit 12.  Without CARRY every chunk does so (no branches: the last one re-requests itself, unused); with it the
     // last chunk runs a body that requests and stages nothing.
     constexpr int NSTAGE = CARRY ? NCH_ - 1 : NCH_;
-    const float *xfrag = lds + j * XS_ + 4 * hh;
+    // SEAM: MFMAs run through the chunk turn.  Chunk c's barrier stands in its unit 15, behind the wait that delivers that unit's
+    // own fragment, and chunk c + 1's first fragment is read right behind it, under unit 15's MFMAs.  Two X sub-buffers are still
+    // enough: every read of buffer c & 1 is complete before barrier(c) -- the last one is the fragment just waited for -- and the
+    // buffer's next writes are chunk c + 1's staging in its unit 12, behind barrier(c); buffer (c + 1) & 1 was written in unit 12
+    // of chunk c -- LDS operations retire in order, so the same wait covers the wave's own writes -- before barrier(c) and is first
+    // read behind it.  Tile top and g image as before: buffer 0 is last read before chunk 6's barrier.  The X request of chunk
+    // c + 2 (17 loads) leaves the chunk top for unit 13 of chunk c, one load behind each MFMA, right behind the staging that frees
+    // its registers and in front of the weight loads of units 13..15, whose waits come four units later; chunk 0 also requests
+    // chunk 1 at its top as before, chunk 6 re-requests chunk 7, unused (no branch: this kernel spills when a main loop gets one).
     auto chunk = [&](int ch, auto stage_tag, auto first_tag) __attribute__((always_inline)) {
       constexpr bool STAGE = decltype(stage_tag)::value, FIRST = decltype(first_tag)::value;
+      constexpr bool XREQ = SEAM && STAGE;
       const float *xb = xfrag + (ch & 1) * XBUF_;
-      if constexpr (STAGE) issue_x(ch + 1 < NCH_ ? ch + 1 : ch);
-      f32x4 bq[2];
-      bq[0] = *reinterpret_cast<const f32x4 *>(xb);
+      if constexpr (STAGE && (!SEAM || FIRST)) issue_x(ch + 1 < NCH_ ? ch + 1 : ch);
+      f32x4 bql[2];
+      f32x4(&bq)[2] = SEAM ? bqc : bql;
+      if constexpr (!SEAM) bq[0] = *reinterpret_cast<const f32x4 *>(xb);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int kg = 0; kg < 4; kg++) {
 #pragma unroll
         for (int comp = 0; comp < 4; comp++) {
           const int u = 4 * kg + comp;
+          if (SEAM && u == 15) {
+            __syncthreads();
+            if constexpr (STAGE) bq[0] = *reinterpret_cast<const f32x4 *>(xfrag + ((ch + 1) & 1) * XBUF_);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          if (XREQ && u == 13) issue_x(ch + 2 < NCH_ ? ch + 2 : NCH_ - 1);
           if (u + 1 < 16) bq[(u + 1) & 1] = *reinterpret_cast<const f32x4 *>(xb + ((u + 1) & 3) * XCOMP_ + ((u + 1) >> 2) * 8);
           // the next chunk's FiLM add / padding / differences / LDS writes ride in the MFMA gaps of unit 12 (the X loads were
           // requested twelve units = 12 k cycles ago)
@@ -333,6 +367,13 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
             }
             __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
           }
+          if (XREQ && u == 13) {                                   // (the seventeenth load behind the last MFMA)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+              __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            }
+          }
           __builtin_amdgcn_sched_barrier(0);
           // the same product's unit of the next k-group takes over this unit's registers (the last k-group wraps to the image's
           // first units: CARRY keeps them for the next tile -- same layer, same image; otherwise unused)
@@ -343,17 +384,17 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     };
     if constexpr (ZERO) {
       chunk(0, std::true_type{}, std::true_type{});
-      __syncthreads();
+      if constexpr (!SEAM) __syncthreads();
     }
 #pragma unroll 1
     for (int ch = ZERO ? 1 : 0; ch < NSTAGE; ch++) {
       chunk(ch, std::true_type{}, std::false_type{});
-      __syncthreads();
+      if constexpr (!SEAM) __syncthreads();
     }
 #pragma unroll 1
     for (int ch = NSTAGE; ch < NCH_; ch++) {
       chunk(ch, std::false_type{}, std::false_type{});
-      __syncthreads();
+      if constexpr (!SEAM) __syncthreads();
     }
 
     // sample of GEMM2 column (ct, j)
@@ -751,7 +792,7 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 
 #ifdef AP_TOOLS
 // the DIET masks the tools build instantiates beside the product's (each item alone on top of its predecessor's product mask)
-#define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150)
+#define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150) X(182)
 static int g_no_q16 = 0;                                        // ap_debug_f32w_q16(0): the 4-byte epilogue for every clip length (A/B)
 static int g_diet = AP_F32W_DIET;                               // ap_debug_f32w_diet(mask): the h'-writing Q16 block with another DIET mask (A/B)
 #else
@@ -822,7 +863,7 @@ extern "C" int ap_debug_resblock_f32w(ap_ctx *ctx, int layer, const float *h_in,
   return ap::launch_resblock_f32w(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
 }
 // the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with the product's DIET mask or one of AP_F32W_AB_MASKS
-// (54 = 22 + pairs, 150 = 22 + no zeroing); every other form keeps
+// (54 = 22 + pairs, 150 = 22 + no zeroing, 182 = both: the product before the seamless chunk turn); every other form keeps
 // the product's mask
 extern "C" int ap_debug_f32w_diet(int mask) {
   bool known = mask == AP_F32W_DIET;

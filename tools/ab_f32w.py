@@ -12,6 +12,10 @@
                                              bit alone on top of it -- 54 (pair gate and transform), 150 (no zeroing of m1, m3, m4) --
                                              and 182 (both: the product); same
                                              method; default FILE profiles/f32w_pk_ab.txt
+   python tools/ab_f32w.py --seam [--out FILE]    MFMAs through the chunk turn: DIET mask 182 (the product before this change) against 1206
+                                             (the chunk's barrier in its last unit, the next chunk's first fragment behind it, X requested
+                                             in MFMA gaps: the product); same method; default FILE profiles/f32w_seam_ab.txt, whose record
+                                             holds the run with the two removed bits (694, 2230) and all three (3766)
    python tools/ab_f32w.py --epilogue [B]    the two epilogue forms: 16-byte stores through LDS patches (clip lengths that are
                                              multiples of four) against the 4-byte form every other length takes"""
 import os
@@ -30,7 +34,8 @@ RECORDS_MARK = "\n== "                                           # the sections 
 DIET = [("parent", None), ("no item", 0), ("carry", 2), ("const", 4), ("both", 6)]
 EDGES = [("parent", None), ("mask 6", 6), ("rows", 22)]
 PK = [("mask 22", 22), ("pairs", 54), ("zero", 150), ("both", 182)]
-PRODUCT_MASK = 182
+SEAM = [("mask 182", 182), ("seam", 1206)]
+PRODUCT_MASK = 1206
 DIET_HEAD = ["F(2,3) fp32 block, GEMM1 diet: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1, h' form, one process,",
              "the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against the parent kernel.",
              "parent = the kernel before the diet (tools/csrc/ap_resblock_f32w_parent.hip); the others are ap_resblock_f32w.hip with DIET mask",
@@ -43,6 +48,10 @@ PK_HEAD = ["F(2,3) fp32 block, fewer vector-ALU issue slots: ms per launch (HIP 
            "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 22.",
            "ap_resblock_f32w.hip with DIET mask 22 (the product before this change), 54 (+ DIET_PK_: output transform and gate on register",
            "pairs), 150 (+ DIET_ZERO_: chunk 0 peeled, m1, m3, m4 start from the instruction's constant 0) and 182 (both: the product).", ""]
+SEAM_HEAD = ["F(2,3) fp32 block, MFMAs through the chunk turn: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1,",
+             "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 182.",
+             "ap_resblock_f32w.hip with DIET mask 182 (the product before this change) and 1206 (+ DIET_SEAM_: the chunk's barrier in its last",
+             "unit, the next chunk's first fragment behind it, the X request in unit 13's gaps: the product).", ""]
 
 
 def setup(B):
@@ -128,10 +137,12 @@ def main():
     if "--epilogue" in sys.argv:
         rest = [a for a in sys.argv[1:] if a != "--epilogue"]
         return epilogue_ab(int(rest[0]) if rest else 256)
-    edges, pk = "--edges" in sys.argv, "--pk" in sys.argv
+    edges, pk, seam = "--edges" in sys.argv, "--pk" in sys.argv, "--seam" in sys.argv
     out = (sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv
-           else os.path.join(ROOT, "profiles", "f32w_pk_ab.txt" if pk else "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
-    if pk:
+           else os.path.join(ROOT, "profiles", "f32w_seam_ab.txt" if seam else "f32w_pk_ab.txt" if pk else "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
+    if seam:
+        diet_ab(out, SEAM, SEAM_HEAD, "mask 182")
+    elif pk:
         diet_ab(out, PK, PK_HEAD, "mask 22")
     elif edges:
         diet_ab(out, EDGES, EDGES_HEAD, "mask 6")

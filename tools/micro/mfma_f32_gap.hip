@@ -5,8 +5,12 @@
 // Second table: the same wave with no MFMA at all -- a stream of independent vector-ALU instructions of one kind (sixteen rotating
 // destinations), shader cycles per instruction: what a two-wide fp32 instruction costs against a one-wide one where the gate and the
 // output transform run (between GEMM1 and GEMM2, the matrix pipe idle).
-//   hipcc --offload-arch=gfx950 -O3 tools/micro/mfma_f32_gap.hip -o /tmp/mfma_f32_gap && /tmp/mfma_f32_gap > profiles/f32w_pk_gap_budget.txt
-//   (profiles/f32w_edges_gap_budget.txt is the first table's first seven columns, from before the packed columns were added)
+// Third table: how far ahead of its use an LDS B fragment has to be read.  One ds_read_b128 per 16 MFMAs on a conflict-free image of
+// 144-byte rows (the block's X image), all four waves of the workgroup reading the same rows, the fragment consumed as the MFMAs' B
+// operand D MFMAs after the read's issue; and an s_barrier among the four waves once per 256 MFMAs.  Sizes DIET_SEAM_ (and the two bits measured beside it: docs/HISTORY.md I.14).
+//   hipcc --offload-arch=gfx950 -O3 tools/micro/mfma_f32_gap.hip -o /tmp/mfma_f32_gap && /tmp/mfma_f32_gap > profiles/f32w_seam_gap_budget.txt
+//   (profiles/f32w_pk_gap_budget.txt is the output from before the load columns and the third table were added,
+//   profiles/f32w_edges_gap_budget.txt the first table's first seven columns, from before the packed columns were)
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -15,9 +19,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-enum { ADD, EXP, DSW, DSR, ST, ADD4, EXP4, PKADD, PKFMA, NKIND };   // ADD4, EXP4: the same fillers in one group of 4 k behind every fourth MFMA
+enum { ADD, EXP, DSW, DSR, ST, ADD4, EXP4, PKADD, PKFMA, LD1, LD4, NKIND };   // ADD4, EXP4: the same fillers in one group of 4 k behind every fourth MFMA
 static const char *const KIND_NAME[NKIND] = {"v_add_f32", "v_exp_f32", "ds_write_b32", "ds_read_b128", "buffer_store_dwordx4",
-                                             "v_add_f32, grouped", "v_exp_f32, grouped", "v_pk_add_f32", "v_pk_fma_f32"};
+                                             "v_add_f32, grouped", "v_exp_f32, grouped", "v_pk_add_f32", "v_pk_fma_f32", "buffer_load_dword",
+                                             "buffer_load_dwordx4"};
 enum { S_ADD, S_FMA, S_MUL, S_EXP, S_PKADD, S_PKFMA, S_PKMUL, NSTREAM };   // the no-MFMA streams
 static const char *const STREAM_NAME[NSTREAM] = {"v_add_f32", "v_fma_f32", "v_mul_f32", "v_exp_f32", "v_pk_add_f32", "v_pk_fma_f32", "v_pk_mul_f32"};
 constexpr int SITERS = 1024;                                      // x 64 instructions
@@ -37,7 +42,8 @@ __global__ __launch_bounds__(256, 1) void gap_kernel(float *__restrict__ sink, l
   for (int i = 0; i < 16; i++) f[i] = seed * i;
   f32x2 f2[16], c2 = {c, c};
   for (int i = 0; i < 16; i++) f2[i] = f32x2{seed * i, seed};
-  f32x4 rd = {seed, seed, seed, seed}, sd = {seed, seed, seed, seed};
+  f32x4 rd = {seed, seed, seed, seed}, sd = {seed, seed, seed, seed}, l4 = {seed, seed, seed, seed};
+  float l1 = seed;
   const unsigned ldsaddr = 16u * tid;                             // this lane's own 16 bytes of LDS
   const unsigned voff = 16u * lane;
   // the wave's own WAVE_BYTES of the sink, and not a byte more: a store past them is dropped by the range check
@@ -61,12 +67,15 @@ __global__ __launch_bounds__(256, 1) void gap_kernel(float *__restrict__ sink, l
         if (KIND == DSW) asm volatile("ds_write_b32 %0, %1" : : "v"(ldsaddr), "v"(b) : "memory");
         if (KIND == DSR) asm volatile("ds_read_b128 %0, %1" : "=v"(rd) : "v"(ldsaddr) : "memory");
         if (KIND == ST) asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" : : "v"(sd), "v"(voff), "s"(rs) : "memory");
+        // (loads of the wave's own slot: in range, one 16-byte slot per lane)
+        if (KIND == LD1) asm volatile("buffer_load_dword %0, %1, %2, 0 offen" : "=v"(l1) : "v"(voff), "s"(rs) : "memory");
+        if (KIND == LD4) asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(l4) : "v"(voff), "s"(rs) : "memory");
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" : "+v"(rd)::"memory");   // (and past the last MFMA's result hazard)
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" : "+v"(rd), "+v"(l1), "+v"(l4)::"memory");   // (and past the last MFMA's result hazard)
   const long long t1 = __builtin_readcyclecounter();
-  float s = rd[0] + rd[1] + rd[2] + rd[3];
+  float s = rd[0] + rd[1] + rd[2] + rd[3] + l1 + l4[0] + l4[1] + l4[2] + l4[3];
   for (int i = 0; i < 16; i++) s += f[i] + f2[i][0] + f2[i][1];
   for (int i = 0; i < 4; i++)
     for (int r = 0; r < 16; r++) s += acc[i][r];
@@ -101,6 +110,55 @@ __global__ __launch_bounds__(256, 1) void stream_kernel(float *__restrict__ sink
   for (int i = 0; i < 16; i++) s += f[i] + f2[i][0] + f2[i][1];
   if (s == 12345.678f) sink[wave * (WAVE_BYTES / 4) + lane] = s;  // (keeps the results alive; inside the wave's own slot)
   if (lane == 0) cycles[wave] = t1 - t0;
+}
+
+
+// One ds_read_b128 per 16 MFMAs, consumed as their B operand D MFMAs after its issue (D < 0: no read at all, the table's base row).
+// The image has the X image's 144-byte rows; the address does not depend on the wave: all four read the same rows.  Two fragment
+// registers alternate, as in the block.  BAR: an s_barrier among the workgroup's four waves behind every 256th MFMA instead.
+constexpr int DITERS = 64;                                        // x 32 MFMAs
+template <int D, bool BAR>
+__global__ __launch_bounds__(256, 1) void dist_kernel(float *__restrict__ sink, long long *__restrict__ cycles, float seed) {
+  __shared__ __attribute__((aligned(16))) float img[32 * 36];
+  const int tid = threadIdx.x, wave = (blockIdx.x * 256 + tid) >> 6, lane = tid & 63;
+  for (int i = tid; i < 32 * 36; i += 256) img[i] = seed;
+  __syncthreads();
+  f32x16 acc[4];
+  for (int i = 0; i < 4; i++)
+    for (int r = 0; r < 16; r++) acc[i][r] = seed;
+  const float a = seed + tid;
+  f32x4 rd[2] = {{seed, seed, seed, seed}, {seed, seed, seed, seed}};
+  const unsigned addr = (unsigned)(size_t)img + 144u * (lane & 31) + 16u * (lane >> 5);
+  const long long t0 = __builtin_readcyclecounter();
+#pragma unroll 1
+  for (int it = 0; it < DITERS; it++) {
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+#pragma unroll
+      for (int m = 0; m < 16; m++) {
+        asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+a"(acc[m & 3]) : "v"(a), "v"(rd[half][m & 3]));
+        if (D >= 0 && m == 15 - D) asm volatile("ds_read_b128 %0, %1" : "=v"(rd[half ^ 1]) : "v"(addr) : "memory");
+      }
+      if (D >= 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rd[half ^ 1])::"memory");
+    }
+    if (BAR && (it & 7) == 7) asm volatile("s_barrier" ::: "memory");
+  }
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 15\n\ts_nop 15" : "+v"(rd[0]), "+v"(rd[1])::"memory");
+  const long long t1 = __builtin_readcyclecounter();
+  float s = rd[0][0] + rd[1][1];
+  for (int i = 0; i < 4; i++)
+    for (int r = 0; r < 16; r++) s += acc[i][r];
+  if (s == 12345.678f) sink[wave * (WAVE_BYTES / 4) + lane] = s;  // (keeps the results alive; inside the wave's own slot)
+  if (lane == 0) cycles[wave] = t1 - t0;
+}
+
+template <int D, bool BAR>
+static double run_dist(float *sink, long long *cyc, int nblk, std::vector<long long> &host) {
+  for (int rep = 0; rep < 2; rep++) dist_kernel<D, BAR><<<nblk, 256>>>(sink, cyc, 0.f);
+  if (hipDeviceSynchronize() != hipSuccess) { fprintf(stderr, "kernel failed\n"); exit(1); }
+  (void)hipMemcpy(host.data(), cyc, host.size() * sizeof(long long), hipMemcpyDeviceToHost);
+  std::sort(host.begin(), host.end());
+  return (double)host[host.size() / 2] / (32.0 * DITERS);
 }
 
 template <int KIND>
@@ -147,6 +205,8 @@ int main() {
   run_kind<EXP4>(sink, cyc, nblk, host, res[EXP4]);
   run_kind<PKADD>(sink, cyc, nblk, host, res[PKADD]);
   run_kind<PKFMA>(sink, cyc, nblk, host, res[PKFMA]);
+  run_kind<LD1>(sink, cyc, nblk, host, res[LD1]);
+  run_kind<LD4>(sink, cyc, nblk, host, res[LD4]);
   const double st[NSTREAM] = {run_stream<S_ADD>(sink, cyc, nblk, host),   run_stream<S_FMA>(sink, cyc, nblk, host),
                               run_stream<S_MUL>(sink, cyc, nblk, host),   run_stream<S_EXP>(sink, cyc, nblk, host),
                               run_stream<S_PKADD>(sink, cyc, nblk, host), run_stream<S_PKFMA>(sink, cyc, nblk, host),
@@ -163,5 +223,17 @@ int main() {
   }
   printf("\nno MFMA: a stream of independent instructions of one kind, one wave per SIMD: shader cycles per instruction (%d per wave)\n\n", 64 * SITERS);
   for (int kind = 0; kind < NSTREAM; kind++) printf("%14s %6.2f\n", STREAM_NAME[kind], st[kind]);
+  const int dist[7] = {0, 1, 2, 3, 4, 8, 15};
+  const double dres[7] = {run_dist<0, false>(sink, cyc, nblk, host), run_dist<1, false>(sink, cyc, nblk, host),
+                          run_dist<2, false>(sink, cyc, nblk, host), run_dist<3, false>(sink, cyc, nblk, host),
+                          run_dist<4, false>(sink, cyc, nblk, host), run_dist<8, false>(sink, cyc, nblk, host),
+                          run_dist<15, false>(sink, cyc, nblk, host)};
+  const double dbase = run_dist<-1, false>(sink, cyc, nblk, host), dbar = run_dist<-1, true>(sink, cyc, nblk, host);
+  printf("\nread-to-use distance: one ds_read_b128 per 16 MFMAs (144-byte rows, the four waves of a workgroup on the same rows), consumed as\n");
+  printf("the B operand D MFMAs after its issue: shader cycles per MFMA (%d MFMAs per wave) and stall per read\n\n", 32 * DITERS);
+  printf("%8s %10.1f\n", "no read", dbase);
+  for (int i = 0; i < 7; i++) printf("D = %4d %10.1f   %+7.1f cycles per read\n", dist[i], dres[i], 16.0 * (dres[i] - dbase));
+  printf("\ns_barrier among the four waves behind every 256th MFMA (no read): %.1f cycles per MFMA, %+.1f cycles per barrier\n", dbar,
+         256.0 * (dbar - dbase));
   return 0;
 }
