@@ -205,7 +205,9 @@ __global__ __launch_bounds__(256) void melspec_htk_kernel(const float *__restric
       const float wgt = fmaxf(0.f, fminf((fr - f0) / (f1 - f0), (f2 - fr) / (f2 - f1)));
       s = __builtin_fmaf(wgt, pw[k], s);
     }
-    out[((size_t)b * n_mels + m) * n_frames + f] = 10.0f * log10f(fmaxf(s, 1e-10f));
+    // under the clamp the value is the constant 10 log10(1e-10): written as -100 (the device's log10f gives -9.999999 for
+    // 1e-10f, AmplitudeToDB on a silent frame gives -100); the same branch as the backward's `s > 1e-10f`
+    out[((size_t)b * n_mels + m) * n_frames + f] = s > 1e-10f ? 10.0f * log10f(s) : -100.0f;
   }
 }
 

@@ -11,6 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from audiopure_amd import synth  # noqa: E402
+from kws_restate import mel_htk_torch as _mel_htk_torch  # noqa: E402  (float64 torch statement of the front-end)
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(ROOT, "tests", "golden", "golden_kws_v1.npz"))
@@ -98,18 +99,6 @@ def test_kws_input_gradient_matches_autograd_of_the_oracle(n_mels, T):
     # the forward value on the autograd route is the same kernel
     with torch.no_grad():
         assert torch.equal(out.detach(), m(x.to(dev)))
-
-
-def _mel_htk_torch(x, n_mels):
-    """float64 torch statement of oracle.kws_oracle.melspec_db_htk, so autograd gives the reference gradient."""
-    from oracle import kws_oracle as K
-    n_fft, hop = 400, 200
-    win = 0.5 - 0.5 * torch.cos(2.0 * np.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft)
-    xp = torch.nn.functional.pad(x[:, None, :], (n_fft // 2, n_fft // 2), mode="reflect")[:, 0]
-    fr = xp.unfold(1, n_fft, hop)[:, :1 + x.shape[1] // hop] * win
-    p = torch.fft.rfft(fr, dim=2).abs() ** 2
-    mel = p @ torch.from_numpy(K.mel_filterbank_htk(n_mels))
-    return 10.0 * torch.log10(torch.clamp(mel, min=1e-10)).transpose(1, 2)
 
 
 @pytest.mark.parametrize("L", [16000, 9999, 777, 401])
