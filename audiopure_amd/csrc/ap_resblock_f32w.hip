@@ -19,7 +19,7 @@
 // accumulator registers; every LDS B fragment (one ds_read_b128 = four k-steps) feeds 16 MFMAs, every 16-byte weight fragment
 // four.  Per chunk of 32 channels: 16 raw 4-byte loads per thread (4 taps x 4 channels of one pair), FiLM add, zero padding,
 // the four input differences, four ds_write_b128 into a [product][column][k] image (144-byte rows: conflict-free 16-byte reads
-// and writes); weights stream L2 -> registers through a ring one k-group (64 MFMAs) deep, requested after the unit that frees
+// and writes) -- in the 16-byte forms four 16-byte loads per thread (one channel, four pairs: DIET_QUAD_ below); weights stream L2 -> registers through a ring one k-group (64 MFMAs) deep, requested after the unit that frees
 // their registers so that no wait on them includes the HBM-latency activation loads issued at the chunk's top.
 // Then: output transform + gate in registers -> g image [column][channel] (1040-byte rows) -> GEMM2 [(C + S) x C].[C x 64]
 // (res rows and skip rows of the wave's 64 channels) -> h' = (h + part_t + res) sqrt(1/2), skip += by memory-side float atomics
@@ -68,8 +68,12 @@ constexpr int DIET_SEAM_ = 1024;         // the chunk's barrier in its last unit
 // (Bit 512, every B fragment pinned a unit ahead of its use, measured 0.04 .. 0.24 % slower in all six cells -- a read one MFMA ahead
 // is already free -- and bit 2048, the staging on channel pairs as 8 v_pk_fma_f32 + 8 v_pk_add_f32 without selects, gained 0.01 ..
 // 0.20 % and stayed inside mask 182's band; neither is in this source: docs/HISTORY.md I.14.)
+// Fewer and wider memory instructions in the main loop (the 16-byte forms; the A/B: profiles/f32w_quad_ab.txt):
+constexpr int DIET_QUAD_ = 4096;         // X staged by (channel, quad of four pairs): four 16-byte loads per chunk in place of sixteen 4-byte ones and part_t's
+// (Bit 8192, a unit's MFMAs by row tile with one weight load behind every fourth, was slower than mask 1206 in three of eight cells --
+// the budget had priced the four loads behind the 16th MFMA at 0.7 cycles a unit -- and is not in this source: docs/HISTORY.md I.15.)
 #ifndef AP_F32W_DIET
-#define AP_F32W_DIET 1206
+#define AP_F32W_DIET 5302
 #endif
 // the 4-byte epilogue form (ragged clip lengths) holds 64 residual values across GEMM2 and has no registers to spare: no item
 constexpr int DIET4_ = 0;
@@ -128,7 +132,9 @@ int launch_pack_f32w(ap_ctx *ctx, hipStream_t st) {
 // rows as 16-byte loads (skip += as a read-modify-write: one workgroup owns a tile within a launch, launches are stream-ordered,
 // so the sum is as deterministic as the float atomics of the 4-byte form).  A CU's store path moves a 4-byte-per-lane store
 // stream at a fraction of its 16-byte rate: the 4-byte epilogue cost 6.5 % of the launch (tools/ab_f32w.py).
-template <bool NOH, bool SAVE = false, bool Q16 = false, int DIET = AP_F32W_DIET>
+// DCLS (DIET_QUAD_ only): the dilation class of the quad staging -- 1: d = 1, 2: d = 2, 4: d >= 4 -- a template argument so that no
+// chunk body branches on the dilation.
+template <bool NOH, bool SAVE = false, bool Q16 = false, int DIET = AP_F32W_DIET, int DCLS = 4>
 __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     const float *__restrict__ hin, const float *__restrict__ pt, float *__restrict__ hout, float *__restrict__ skip,
     const float *__restrict__ w1w, const float *__restrict__ b1, const float *__restrict__ w2w,
@@ -139,7 +145,9 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   constexpr bool PK = Q16 && (DIET & DIET_PK_) != 0;
   constexpr bool ZERO = Q16 && (DIET & DIET_ZERO_) != 0;
   constexpr bool SEAM = Q16 && (DIET & DIET_SEAM_) != 0;
+  constexpr bool QUAD = Q16 && (DIET & DIET_QUAD_) != 0;
   static_assert(!SEAM || (CARRY && ZERO), "DIET_SEAM_ is written for the peeled first and last chunk");
+  static_assert(!QUAD || (SEAM && CONST), "DIET_QUAD_ takes part_t from the LDS copy and its place in the chunk from DIET_SEAM_");
   // LDS map (floats): X sub-buffers 0, 1 | g image | Q16: output patches | CONST: b1, b2, part_t
   constexpr int COFF_ = Q16 ? LDS_FLOATS_Q16_ : LDS_FLOATS_;
   __shared__ __attribute__((aligned(16))) float lds[COFF_ + (CONST ? NCONST_ : 0)];
@@ -149,6 +157,11 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, hh = lane >> 5;
   const int sq = tid >> 5;                                       // staging: channel quad of the chunk (0..7); j = the pair
+  // QUAD staging: channel xc of the chunk's 32, pairs 4 xq .. 4 xq + 3 of the tile's 32.  A wave is 16 channels x 4 quads with the
+  // quad as the fast lane index: four neighbouring lanes load 64 consecutive bytes, which a 16-byte load per MFMA gap needs to be free
+  // (with the channel fast it costs 256 cycles: profiles/f32w_quad_gap_budget.txt); a ds_write_b32 of one (product, pair of the quad)
+  // goes to bank (16 quad + channel + const) mod 32 -- two lanes per bank in a 32-lane group, which costs this write nothing
+  const int xc = 16 * (wave & 1) + (lane >> 2), xq = 4 * (wave >> 1) + (lane & 3);
   const int d = 1 << logd;
 
   // ---- tile walk: each XCD (workgroups g, g + 8, ... share one) takes a contiguous run of (clip, tile) work, its CUs walking
@@ -204,6 +217,8 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
   auto ld_b1 = [&](int idx) { if constexpr (CONST) return ld_c(idx); else return ld4(b1rs, idx); };
   auto ld_b2 = [&](int idx) { if constexpr (CONST) return ld_c(2 * C + idx); else return ld4(b2rs, idx); };
   auto ld_pt = [&](int idx) { if constexpr (CONST) return ld_c(4 * C + idx); else return ld4(ptrs, idx); };
+  int cptx = COFF_ + 4 * C + xc;                                 // QUAD: this thread's part_t of chunk 0 in the LDS copy (opaque, as cbase)
+  if constexpr (QUAD) asm volatile("" : "+v"(cptx));
 
   auto load_a1 = [&](f32x4(&a)[4], unsigned unit) {             // one (k-group, product) unit of GEMM1 weights: 4 row tiles
 #pragma unroll
@@ -229,18 +244,34 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     b = __builtin_amdgcn_readfirstlane(tile / ntiles);
     p0 = __builtin_amdgcn_readfirstlane((tile % ntiles) * NP_);
     hrs = uni_rsrc(hin + (size_t)b * C * L, clip_bytes);
-    const int p = p0 + j;                                        // staging geometry of this thread's pair
+    // staging geometry of this thread's pair.  QUAD (L % 4 == 0): of its four pairs.  d >= 4: their first outputs are tf .. tf + 3,
+    // tf % 4 == 0, so tap k of the quad is the aligned 16-byte piece at tf + (k - 1) d; d = 1, 2: tf % 8 == 0 and all sixteen taps lie
+    // in the four aligned pieces of [tf - 4, tf + 12).  Every piece is wholly inside the clip or wholly outside; an outside piece gets
+    // the offset no descriptor reaches (the load answers +0) and never a clamped or wrapped address
+    const int p = QUAD ? p0 + 4 * xq : p0 + j;
     const int tf = ((p >> logd) << (logd + 1)) + (p & (d - 1));
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-      const int tp = tf + (k - 1) * d;
+      const int tp = tf + (k - 1) * (QUAD && DCLS < 4 ? 4 : d);
       tok[k] = (tp >= 0) && (tp < L);
-      voff[k] = ((unsigned)min(max(tp, 0), L - 1) + (unsigned)(4 * sq) * (unsigned)L) * 4u;
+      if constexpr (QUAD) voff[k] = tok[k] ? ((unsigned)tp + (unsigned)xc * (unsigned)L) * 4u : 0x80000000u;
+      else voff[k] = ((unsigned)min(max(tp, 0), L - 1) + (unsigned)(4 * sq) * (unsigned)L) * 4u;
     }
   };
     float xr[4][4];                                              // [channel of the quad][tap]
     f32x4 ptq;
+    f32x4 xv[4];                                                 // QUAD: the four pieces (d >= 4: [tap][pair of the quad])
+    float ptc;
+    f32x2 su[8], sc[8];                                          // QUAD: u = x + part_t on sample pairs; the products (live in unit 12 only)
+    float ptm[4], sc0[4], sc3[4];
     auto issue_x = [&](int ch) {
+      if constexpr (QUAD) {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          xv[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(hrs, voff[k], ch * KCW_ * L * 4, 0));
+        ptc = lds[cptx + ch * KCW_];
+        return;
+      }
       ptq = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ptrs, (unsigned)(16 * sq), ch * KCW_ * 4, 0));
 #pragma unroll
       for (int cc = 0; cc < 4; cc++)
@@ -248,7 +279,69 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
         for (int k = 0; k < 4; k++)
           xr[cc][k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hrs, voff[k], (ch * KCW_ + cc) * L * 4, 0));
     };
+    // QUAD: the staging in sixteen steps, one per MFMA gap of unit 12 (all of them in a row at the tile top).  u = x + part_t is the
+    // same add as below inside the clip; outside it x = +0 and the masked part_t is 0: 0 + 0 = +0 whatever part_t's sign.  Sample
+    // pairs run as v_pk_add_f32, written as instructions: in an MFMA's shadow the compiler splits the ones it selects itself.  Step
+    // 0: the four selects; 1..3: u (w = sample pair of the window: d >= 4 piece w / 2 = tap, else pairs 1..6 of [tf - 4, tf + 12));
+    // 4..7: the products; 8..15: two ds_write_b32 each into the unchanged [product][column][k] image.
+    //   d >= 4: pairs (2h, 2h + 1) have tap k in pair 2k + h;     d = 2: the same pairs have tap k in pair 1 + 2h + k;
+    //   d = 1: pair i has its taps at samples 2i + 3 .. 2i + 6 of the window: m2, m3 from sample pair i + 2 alone, m1, m4 one-wide
+    auto stage = [&](float *dst, int g) __attribute__((always_inline)) {
+      auto pk_add = [](f32x2 x, f32x2 y) { f32x2 r; asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r; };
+      auto pk_sub = [](f32x2 x, f32x2 y) { f32x2 r; asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(x), "v"(y)); return r; };
+      auto pk_bc = [](f32x2 x, float y) {                        // x + (y, y): the second operand's low half twice, its high half is not read
+        f32x2 r;
+        f32x2 y2 = __builtin_nondeterministic_value(r);
+        y2[0] = y;
+        asm volatile("v_pk_add_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(r) : "v"(x), "v"(y2));
+        return r;
+      };
+      auto pk_sumdiff = [](f32x2 x) {                             // (x0 + x1, x1 - x0)
+        f32x2 r;
+        asm volatile("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(x));
+        return r;
+      };
+      auto half = [&](int w) { return w & 1 ? f32x2{xv[w >> 1][2], xv[w >> 1][3]} : f32x2{xv[w >> 1][0], xv[w >> 1][1]}; };
+      constexpr int W0 = DCLS == 4 ? 0 : 1, NW = DCLS == 4 ? 8 : 6;   // the sample pairs that are used
+      if (g == 0) {
+        asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(ptc));   // (pins the wait for the loads here, as below)
+#pragma unroll
+        for (int k = 0; k < 4; k++) ptm[k] = tok[k] ? ptc : 0.f;
+      } else if (g <= 3) {
+#pragma unroll
+        for (int w = W0 + 3 * (g - 1); w < W0 + 3 * g && w < W0 + NW; w++) su[w] = pk_bc(half(w), ptm[w >> 1]);
+      } else if (g <= 7) {
+        if constexpr (DCLS == 1) {
+          const int i = g - 4;
+          sc[i] = pk_sumdiff(su[i + 2]);
+          sc0[i] = su[i + 1][1] - su[i + 2][1];
+          sc3[i] = su[i + 3][0] - su[i + 2][0];
+        } else {
+          const int h = (g - 4) >> 1;
+          auto tap = [&](int k) { return DCLS == 4 ? su[2 * k + h] : su[1 + 2 * h + k]; };
+          if (((g - 4) & 1) == 0) sc[4 * h + 0] = pk_sub(tap(0), tap(2)), sc[4 * h + 1] = pk_add(tap(1), tap(2));
+          else sc[4 * h + 2] = pk_sub(tap(2), tap(1)), sc[4 * h + 3] = pk_sub(tap(3), tap(1));
+        }
+      } else {
+        float *q = dst + 4 * xq * XS_ + xc;
+        const int w = g - 8;
+        if constexpr (DCLS == 1) {
+          const int i = w >> 1;
+          if ((w & 1) == 0) q[i * XS_] = sc0[i], q[i * XS_ + XCOMP_] = sc[i][0];
+          else q[i * XS_ + 2 * XCOMP_] = sc[i][1], q[i * XS_ + 3 * XCOMP_] = sc3[i];
+        } else {
+          const int h = w >> 2, comp = w & 3;
+          q[2 * h * XS_ + comp * XCOMP_] = sc[4 * h + comp][0];
+          q[(2 * h + 1) * XS_ + comp * XCOMP_] = sc[4 * h + comp][1];
+        }
+      }
+    };
     auto store_x = [&](float *dst) {                             // FiLM add (WaveNet.py:84), zero padding (:26-27), input differences
+      if constexpr (QUAD) {
+#pragma unroll
+        for (int g = 0; g < 16; g++) stage(dst, g);
+        return;
+      }
       // (the loaded values pass through an empty asm: it pins this arithmetic -- and the wait for the loads -- HERE; instruction
       // selection would otherwise place it right behind the loads, half a chunk early)
       asm volatile("" : "+v"(xr[0][0]), "+v"(xr[0][1]), "+v"(xr[0][2]), "+v"(xr[0][3]), "+v"(xr[1][0]), "+v"(xr[1][1]), "+v"(xr[1][2]),
@@ -326,6 +419,11 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
     // c + 2 (17 loads) leaves the chunk top for unit 13 of chunk c, one load behind each MFMA, right behind the staging that frees
     // its registers and in front of the weight loads of units 13..15, whose waits come four units later; chunk 0 also requests
     // chunk 1 at its top as before, chunk 6 re-requests chunk 7, unused (no branch: this kernel spills when a main loop gets one).
+    // QUAD: the request is four 16-byte loads in unit 13's first four gaps, and the staging's LDS writes are sixteen ds_write_b32 in
+    // gaps 8..15 of unit 12 instead of four ds_write_b128 behind its last MFMA.  The argument above holds as it stands: the writes of
+    // chunk c + 1's image still go to buffer (c + 1) & 1, whose last read was waited for before barrier(c - 1) and which nobody reads
+    // again before barrier(c); they are all issued in unit 12, three units before barrier(c) in unit 15, and the wait in front of that
+    // barrier retires them with the fragment it delivers.  part_t comes from the launch constants' LDS copy, read with the request.
     auto chunk = [&](int ch, auto stage_tag, auto first_tag) __attribute__((always_inline)) {
       constexpr bool STAGE = decltype(stage_tag)::value, FIRST = decltype(first_tag)::value;
       constexpr bool XREQ = SEAM && STAGE;
@@ -349,17 +447,24 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
           if (u + 1 < 16) bq[(u + 1) & 1] = *reinterpret_cast<const f32x4 *>(xb + ((u + 1) & 3) * XCOMP_ + ((u + 1) >> 2) * 8);
           // the next chunk's FiLM add / padding / differences / LDS writes ride in the MFMA gaps of unit 12 (the X loads were
           // requested twelve units = 12 k cycles ago)
-          if (STAGE && u == 12) store_x(lds + ((ch + 1) & 1) * XBUF_);
+          if (STAGE && u == 12 && !QUAD) store_x(lds + ((ch + 1) & 1) * XBUF_);
+          auto mfma = [&](int rt, int e) __attribute__((always_inline)) {
+            if (FIRST && kg == 0 && e == 0 && comp != 1)           // (m2 starts from the bias)
+              acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], f32x16{}, 0, 0, 0);
+            else
+              acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], acc[comp][rt], 0, 0, 0);
+          };
 #pragma unroll
           for (int e = 0; e < 4; e++)
 #pragma unroll
             for (int rt = 0; rt < 4; rt++) {
-              if (FIRST && kg == 0 && e == 0 && comp != 1)         // (m2 starts from the bias)
-                acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], f32x16{}, 0, 0, 0);
-              else
-                acc[comp][rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[comp][rt][e], bq[u & 1][e], acc[comp][rt], 0, 0, 0);
+              mfma(rt, e);
+              if (QUAD && STAGE && u == 12) {                      // one step of the staging behind each MFMA, in this order
+                stage(lds + ((ch + 1) & 1) * XBUF_, 4 * e + rt);
+                __builtin_amdgcn_sched_barrier(0);
+              }
             }
-          if (STAGE && u == 12) {
+          if (STAGE && u == 12 && !QUAD) {
 #pragma unroll
             for (int i = 0; i < 16; i++) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -367,9 +472,9 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
             }
             __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
           }
-          if (XREQ && u == 13) {                                   // (the seventeenth load behind the last MFMA)
+          if (XREQ && u == 13) {                                   // (not QUAD: the seventeenth load behind the last MFMA; QUAD: four loads, four gaps)
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
+            for (int i = 0; i < (QUAD ? 4 : 16); i++) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
               __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
@@ -792,12 +897,22 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 
 #ifdef AP_TOOLS
 // the DIET masks the tools build instantiates beside the product's (each item alone on top of its predecessor's product mask)
-#define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150) X(182)
+#define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150) X(182) X(1206)
 static int g_no_q16 = 0;                                        // ap_debug_f32w_q16(0): the 4-byte epilogue for every clip length (A/B)
 static int g_diet = AP_F32W_DIET;                               // ap_debug_f32w_diet(mask): the h'-writing Q16 block with another DIET mask (A/B)
 #else
 static constexpr int g_no_q16 = 0;
 #endif
+
+// one 16-byte form at DIET mask M; with DIET_QUAD_ the instantiation of the layer's dilation class
+template <bool NOH, bool SAVE, int M, class... A>
+static void launch_q16(unsigned grid, hipStream_t st, int logd, A... args) {
+  if constexpr ((M & DIET_QUAD_) != 0) {
+    if (logd == 0) return resblock_f32w_kernel<NOH, SAVE, true, M, 1><<<grid, 256, 0, st>>>(args...);
+    if (logd == 1) return resblock_f32w_kernel<NOH, SAVE, true, M, 2><<<grid, 256, 0, st>>>(args...);
+  }
+  resblock_f32w_kernel<NOH, SAVE, true, M><<<grid, 256, 0, st>>>(args...);
+}
 
 bool resblock_f32w_serves(const ap_ctx *ctx, int B, int L) {
   if (ctx->cfg.precision != AP_PREC_F32 || ctx->f32_form != 1 || ctx->C != WC_ || ctx->S != WC_ || !ctx->w1w) return false;
@@ -825,7 +940,7 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
   const bool q16 = (L & 3) == 0 && !g_no_q16;
   if (aout) {
     if (!hout) { set_error("resblock (save): needs an h' buffer"); return -22; }
-    if (q16) resblock_f32w_kernel<false, true, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
+    if (q16) launch_q16<false, true, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
     else resblock_f32w_kernel<false, true, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
     AP_HIP(hipGetLastError());
     return 0;
@@ -833,17 +948,17 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
 #ifdef AP_TOOLS
 #define AP_F32W_AB(M)                                                                                                             \
   if (hout && q16 && g_diet == M) {                                                                                               \
-    resblock_f32w_kernel<false, false, true, M><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, \
-                                                                      ntiles, (int)nblk, nullptr);                                \
+    launch_q16<false, false, M>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk,    \
+                                (float *)nullptr);                                                                                \
     AP_HIP(hipGetLastError());                                                                                                    \
     return 0;                                                                                                                     \
   }
   AP_F32W_AB_MASKS(AP_F32W_AB)
 #undef AP_F32W_AB
 #endif
-  if (hout && q16) resblock_f32w_kernel<false, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  if (hout && q16) launch_q16<false, false, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, (float *)nullptr);
   else if (hout) resblock_f32w_kernel<false, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
-  else if (q16) resblock_f32w_kernel<true, false, true><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  else if (q16) launch_q16<true, false, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, (float *)nullptr);
   else resblock_f32w_kernel<true, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
   AP_HIP(hipGetLastError());
   return 0;

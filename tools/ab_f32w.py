@@ -16,6 +16,10 @@
                                              (the chunk's barrier in its last unit, the next chunk's first fragment behind it, X requested
                                              in MFMA gaps: the product); same method; default FILE profiles/f32w_seam_ab.txt, whose record
                                              holds the run with the two removed bits (694, 2230) and all three (3766)
+   python tools/ab_f32w.py --quad [--out FILE]    wider and fewer memory instructions: DIET mask 1206 (the product before this change) against
+                                             5302 (X staged by channel and pair quad, four 16-byte loads per chunk: the product); same
+                                             method, layers 0, 2, 5, 11; default FILE profiles/f32w_quad_ab.txt, whose record holds the run
+                                             with the removed bit (9398) and both (13494)
    python tools/ab_f32w.py --epilogue [B]    the two epilogue forms: 16-byte stores through LDS patches (clip lengths that are
                                              multiples of four) against the 4-byte form every other length takes"""
 import os
@@ -35,7 +39,8 @@ DIET = [("parent", None), ("no item", 0), ("carry", 2), ("const", 4), ("both", 6
 EDGES = [("parent", None), ("mask 6", 6), ("rows", 22)]
 PK = [("mask 22", 22), ("pairs", 54), ("zero", 150), ("both", 182)]
 SEAM = [("mask 182", 182), ("seam", 1206)]
-PRODUCT_MASK = 1206
+QUAD = [("mask 1206", 1206), ("quad", 5302)]
+PRODUCT_MASK = 5302
 DIET_HEAD = ["F(2,3) fp32 block, GEMM1 diet: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1, h' form, one process,",
              "the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against the parent kernel.",
              "parent = the kernel before the diet (tools/csrc/ap_resblock_f32w_parent.hip); the others are ap_resblock_f32w.hip with DIET mask",
@@ -52,6 +57,10 @@ SEAM_HEAD = ["F(2,3) fp32 block, MFMAs through the chunk turn: ms per launch (HI
              "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 182.",
              "ap_resblock_f32w.hip with DIET mask 182 (the product before this change) and 1206 (+ DIET_SEAM_: the chunk's barrier in its last",
              "unit, the next chunk's first fragment behind it, the X request in unit 13's gaps: the product).", ""]
+QUAD_HEAD = ["F(2,3) fp32 block, wider and fewer memory instructions: ms per launch (HIP events, 6 launches after 2), L = 16000, accumulate = 1,",
+             "h' form, one process, the variants interleaved within each repeat; median of 3 repeats [min .. max]; gain against mask 1206.",
+             "ap_resblock_f32w.hip with DIET mask 1206 (the product before this change) and 5302 (+ DIET_QUAD_: X staged by (channel, quad of",
+             "four pairs), four 16-byte loads per chunk, part_t from the LDS copy, packed adds: the product).", ""]
 
 
 def setup(B):
@@ -95,14 +104,14 @@ def epilogue_ab(B):
             print(f"layer {layer:2d}  16-byte epilogue: {t16:7.3f} ms   4-byte epilogue: {t4:7.3f} ms", flush=True)
 
 
-def diet_ab(out, DIET=DIET, head=DIET_HEAD, base_name="parent"):
+def diet_ab(out, DIET=DIET, head=DIET_HEAD, base_name="parent", layers=(0, 5, 11)):
     lines = list(head)
     for B in (256, 512):
         net, eng, (hd, pt, hout, sk, B, L) = setup(B)
         lib = eng.lib
         lib.ap_debug_f32w_diet.argtypes = [C.c_int]
         lib.ap_debug_resblock_f32w_parent.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 2
-        for layer in (0, 5, 11):
+        for layer in layers:
             new = lambda: N.check(lib.ap_resblock_fwd(eng.ctx, layer, N.ptr(hd), N.ptr(pt), N.ptr(hout), N.ptr(sk), 1, B, L, N.stream()))
             old = lambda: N.check(lib.ap_debug_resblock_f32w_parent(eng.ctx, layer, N.ptr(hd), N.ptr(pt), N.ptr(hout), N.ptr(sk), 1, B, L,
                                                                     N.stream(), None))
@@ -137,10 +146,12 @@ def main():
     if "--epilogue" in sys.argv:
         rest = [a for a in sys.argv[1:] if a != "--epilogue"]
         return epilogue_ab(int(rest[0]) if rest else 256)
-    edges, pk, seam = "--edges" in sys.argv, "--pk" in sys.argv, "--seam" in sys.argv
+    edges, pk, seam, quad = "--edges" in sys.argv, "--pk" in sys.argv, "--seam" in sys.argv, "--quad" in sys.argv
     out = (sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv
-           else os.path.join(ROOT, "profiles", "f32w_seam_ab.txt" if seam else "f32w_pk_ab.txt" if pk else "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
-    if seam:
+           else os.path.join(ROOT, "profiles", "f32w_quad_ab.txt" if quad else "f32w_seam_ab.txt" if seam else "f32w_pk_ab.txt" if pk else "f32w_edges_ab.txt" if edges else "f32w_diet_ab.txt"))
+    if quad:
+        diet_ab(out, QUAD, QUAD_HEAD, "mask 1206", layers=(0, 2, 5, 11))
+    elif seam:
         diet_ab(out, SEAM, SEAM_HEAD, "mask 182")
     elif pk:
         diet_ab(out, PK, PK_HEAD, "mask 22")
