@@ -15,6 +15,7 @@ sys.path.insert(1, os.path.dirname(os.path.abspath(__file__)))
 from audiopure_amd import synth  # noqa: E402
 from audiopure_amd import _native as N  # noqa: E402
 import train_restate as T  # noqa: E402
+from wgrad_restate import corr_reference  # noqa: E402  (the float64 einsum: shared with test_gpu_wgrad_edges.py)
 from test_train_cpu import check_against_golden  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -41,24 +42,6 @@ def _net(cfg, dev, seed=0):
 
 
 # ---- 1. ap_wgrad_corr -----------------------------------------------------------------------------------------
-def corr_reference(P, Q, film, taps, dil, mode):
-    """G[m][n][k] = sum_{b,t} P[b][m][t] Q~[b][n][t + (k - taps/2) dil] in float64; Q~ zero outside [0, L)."""
-    P, Q = P.double(), Q.double()
-    B, M, L = P.shape
-    if mode == FILM:
-        Q = Q + film.double().view(1, -1, 1)
-    elif mode == GATE:
-        Nn = Q.shape[1] // 2
-        Q = torch.tanh(Q[:, :Nn]) * torch.sigmoid(Q[:, Nn:])
-    G = torch.zeros(M, Q.shape[1], taps, dtype=torch.float64)
-    for k in range(taps):
-        off = (k - taps // 2) * dil
-        lo, hi = max(0, -off), min(L, L - off)                    # t with 0 <= t + off < L
-        if lo < hi:
-            G[:, :, k] = torch.einsum("bmt,bnt->mn", P[:, :, lo:hi], Q[:, :, lo + off:hi + off])
-    return G
-
-
 CORR_CASES = [(64, 32, 3, 1, 1, 37, PLAIN), (512, 256, 3, 4, 2, 640, FILM), (32, 32, 3, 8, 2, 129, FILM),
               (512, 256, 3, 2048, 2, 300, FILM), (256, 256, 1, 1, 3, 777, GATE)]
 
@@ -117,13 +100,29 @@ def test_rowsum_matches_float64_autograd(dev, weighting):
     """Each weighting as the gradient it serves, by float64 autograd: a bias (w = 1), a per-row scale of a second tensor, of a
     broadcast row, and the init conv's weight / bias behind its ReLU (WaveNet.py:147,168).  Bound: thread i adds ceil(n / 256)
     terms in turn, then eight tree levels, plus the product's and the scale's roundings: (ceil(n / 256) + 10) 2^-24 sum|terms|."""
+    _rowsum_case(dev, weighting, 3, 5, 777)
+
+
+@pytest.mark.parametrize("B,M,L", [(1, 1, 1), (2, 3, 255), (1, 2, 257)])
+@pytest.mark.parametrize("weighting", ["one", "broadcast+mask"])
+def test_rowsum_at_the_edges_of_its_strided_loop(dev, weighting, B, M, L):
+    """One element (255 threads add nothing), one short of and one past the 256-thread stride; the same bound formula.  The mask
+    holds +0.0 and -0.0, which `> 0` both drops."""
+    _rowsum_case(dev, weighting, B, M, L, zeros_in_mask=True)
+
+
+def _rowsum_case(dev, weighting, B, M, L, zeros_in_mask=False):
     lib = N.lib()
-    B, M, L = 3, 5, 777
-    A, W, Wb = U("rsA", (B, M, L)), U("rsW", (B, M, L)), U("rsWb", (B, 1, L))
-    w0, b0 = U("rsw0", (M,)), U("rsb0", (M,), -0.3, 0.3)
+    k = "" if (B, M, L) == (3, 5, 777) else f".{B}.{M}.{L}"
+    A, W, Wb = U("rsA" + k, (B, M, L)), U("rsW" + k, (B, M, L)), U("rsWb" + k, (B, 1, L))
+    w0, b0 = U("rsw0" + k, (M,)), U("rsb0" + k, (M,), -0.3, 0.3)
     p = torch.ones(M, dtype=torch.float64, requires_grad=True)
     A64 = A.double()
     h0 = torch.relu(w0.view(1, M, 1) * Wb + b0.view(1, M, 1))                   # fp32, as ap_init_conv forms it
+    if zeros_in_mask and h0.numel() >= 3:
+        h0.view(-1)[1::5] = 0.0
+        h0.view(-1)[2::5] = -0.0
+        assert bool(torch.signbit(h0[h0 == 0]).any()) and not bool(torch.signbit(h0[h0 == 0]).all())
     if weighting == "one":
         f, args = (A64 * (W.double() + p.view(1, M, 1))).sum(), (None, None, 0)
     elif weighting == "tensor":
@@ -184,6 +183,28 @@ def test_weight_norm_bwd_matches_float64_autograd(dev, rows, cols):
         assert float(dv_ref.abs().max()) < 1e-12 and torch.count_nonzero(dv).item() == 0
 
 
+@pytest.mark.parametrize("rows,cols", [(5, 300), (4, 2)])
+def test_weight_norm_bwd_of_an_all_zero_row_is_zero_not_nan(dev, rows, cols):
+    """Row 1 of v is all zero: it has no direction, and the kernel gives dg = 0 and dv = 0 exactly there (autograd gives NaN).  The
+    other rows against float64 autograd under the per-tensor rule; more than one 256-thread stride of columns, and two columns."""
+    lib = N.lib()
+    v, g, dW = U(f"wnzv{rows}.{cols}", (rows, cols)).clone(), U(f"wnzg{rows}", (rows, 1), 0.5, 1.5), U(f"wnzd{rows}.{cols}", (rows, cols))
+    v[1] = 0.0
+    keep = [r for r in range(rows) if r != 1]
+    v64, g64 = v[keep].double().requires_grad_(True), g[keep].double().requires_grad_(True)
+    W = v64 * (g64 / v64.norm(dim=1, keepdim=True))
+    dg_ref, dv_ref = torch.autograd.grad(W, (g64, v64), dW[keep].double())
+    dg, dv = torch.full((rows, 1), float("nan"), device=dev), torch.full((rows, cols), float("nan"), device=dev)
+    dWd, vd, gd = dW.to(dev), v.to(dev), g.to(dev)
+    N.check(lib.ap_weight_norm_bwd(N.ptr(dWd), N.ptr(vd), N.ptr(gd), N.ptr(dg), N.ptr(dv), rows, cols, N.stream()), "ap_weight_norm_bwd")
+    dg, dv = dg.cpu(), dv.cpu()
+    assert torch.isfinite(dg).all() and torch.isfinite(dv).all()
+    assert float(dg[1].abs().max()) == 0.0 and torch.count_nonzero(dv[1]).item() == 0
+    G = max(float(dg_ref.abs().max()), float(dv_ref.abs().max()))
+    T.check_tensor("dg", dg[keep], dg_ref, G)
+    T.check_tensor("dv", dv[keep], dv_ref, G)
+
+
 def test_embed_bwd_matches_float64_autograd(dev):
     """Embed dims 128 / 512 / 512: fc_t of every layer, then swish(fc_t2(swish(fc_t1(.)))), from a random dpart."""
     cfg = synth.mini_wavenet_config(64, 3, 12)
@@ -225,6 +246,30 @@ def test_embed_bwd_matches_float64_autograd(dev):
     G = max(float(v.abs().max()) for v in ref.values())
     for k in names:
         T.check_tensor(k, got[k].cpu() / 2, ref[k], G)
+
+
+def test_embed_bwd_without_accumulate_overwrites(dev):
+    """accumulate = 0 into NaN-filled outputs gives the bits that the first accumulate = 1 call gives onto zeros."""
+    cfg = synth.mini_wavenet_config(64, 3, 12)
+    net, _ = _net(cfg, dev, seed=2)
+    eng = net.engine()
+    lib, NL, C_, E = eng.lib, 3, 64, 512
+    step = 37.0
+    part = torch.empty(NL * C_ + E, device=dev)
+    N.check(lib.ap_embed(eng.ctx, step, N.ptr(part), N.stream()), "ap_embed")
+    scratch, dpd = torch.empty(lib.ap_embed_bwd_scratch_elems(eng.ctx), device=dev), U("edp", (NL, C_)).double().to(dev)
+    shapes = [(NL, C_, E), (NL, C_), (512, 128), (512,), (512, 512), (512,)]
+
+    def run(fill, accumulate):
+        outs = [torch.full(s, fill, device=dev) for s in shapes]
+        N.check(lib.ap_embed_bwd(eng.ctx, step, dpd.data_ptr(), N.ptr(part[NL * C_:]), *(N.ptr(t) for t in outs), N.ptr(scratch), accumulate,
+                                 N.stream()), "ap_embed_bwd")
+        return outs
+
+    added, written = run(0.0, 1), run(float("nan"), 0)
+    for a, w in zip(added, written):
+        assert torch.isfinite(w).all() and float(w.abs().max()) > 0
+        assert torch.equal(a, w)
 
 
 # ---- 3. - 5. training_loss ------------------------------------------------------------------------------------
