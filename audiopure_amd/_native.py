@@ -156,6 +156,12 @@ SIGNATURES = {
     "ap_m5_train_fwd": (_i, [_vp, _fp, _fp, _fp, _fp, _f, _vp, _sz, _i, _i, _i, _vp]),
     "ap_m5_train_bwd": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _vp, _sz, _i, _i, _vp]),
     "ap_weight_norm_bwd": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
+    "ap_conv2d_wgrad_workspace_bytes": (_sz, [_i] * 10),
+    "ap_conv2d_wgrad": (_i, [_fp, _fp, _fp, _vp, _sz] + [_i] * 13 + [_vp]),
+    "ap_conv2d_pack_bwd": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _vp]),
+    "ap_bn2d_train_workspace_bytes": (_sz, [_i]),
+    "ap_bn2d_train_fwd": (_i, [_fp] * 7 + [_vp, _sz, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "ap_bn2d_train_bwd": (_i, [_fp] * 8 + [_vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _LIB = None

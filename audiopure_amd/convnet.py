@@ -8,7 +8,13 @@ at the ATen level (``TorchDispatchMode`` — immune to how the Python is written
 ``.forward`` directly), BatchNorm is folded into the preceding conv (or becomes a per-channel affine), ReLU / residual
 adds are fused where the graph allows, and the resulting plan runs on the HIP primitives of ``include/audiopure.h``
 (``ap_conv2d_fwd`` = conv-as-GEMM on the fp32 MFMA, ``ap_affine_nchw``, ``ap_add_nchw``, ``ap_copy_channels``,
-``ap_pool2d``).  PyTorch allocates the buffers; no torch operator runs in ``forward``.
+``ap_pool2d``).  PyTorch allocates the buffers; no torch operator runs in the eval ``forward``.
+
+In ``train()`` mode (``train_speech_commands.py:122-153``) the same tape is lowered to a *train plan* instead
+(``lower(module, chw, train=True)``): BatchNorm stays a ``bn`` step on batch statistics (``ap_bn2d_train_fwd`` / ``_bwd``), the plan
+names the module's live parameters, and the reverse sweep also leaves every parameter gradient (``ap_conv2d_wgrad``, ``ap_rowsum``).
+The train step's torch operators are bookkeeping only: one fused increment of the ``num_batches_tracked`` counters per forward and the
+zero fill of each gradient buffer of the sweep.
 """
 from __future__ import annotations
 
@@ -63,7 +69,7 @@ class Val:
 
 @dataclass
 class Step:
-    kind: str                      # conv | affine | add | copy | pool
+    kind: str                      # conv | affine | add | copy | pool | bn (train plans only)
     out: Val = None
     ins: list = field(default_factory=list)
     p: dict = field(default_factory=dict)
@@ -77,6 +83,7 @@ class Plan:
         self.input: Val = None
         self.output: Val = None
         self.weights = {}              # name -> host tensor (folded conv weights / biases / affine vectors)
+        self.train = False             # a train plan: BatchNorm is a `bn` step, parameters are NAMED (state-dict keys), nothing cloned
 
     def new_buf(self, C, H, W) -> Val:
         b = self.nbuf
@@ -96,9 +103,26 @@ def _need(cond, what: str) -> None:
         raise NotImplementedError("convnet lowering: " + what)
 
 
-def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
-    """Record one eval forward of `module` on a CPU example [2, C, H, W] and turn it into a Plan."""
-    m = copy.deepcopy(module).to("cpu").float().eval()
+def _train_checks(m: nn.Module):
+    """What the train plan does not serve, as ``NotImplementedError`` before anything is traced."""
+    bn_of = {}
+    for mod in m.modules():
+        if isinstance(mod, (nn.Dropout, nn.Dropout2d, nn.AlphaDropout)) and mod.p > 0:
+            raise NotImplementedError("convnet lowering: live dropout (nn.Dropout(p > 0) in train() mode) has no kernel")
+        if isinstance(mod, nn.modules.batchnorm._BatchNorm):
+            _need(mod.affine, "BatchNorm(affine=False) is not served in train() mode")
+            _need(mod.track_running_stats and mod.running_mean is not None, "BatchNorm(track_running_stats=False) is not served in train() mode")
+            bn_of[id(mod.running_mean)] = mod
+    return bn_of
+
+
+def lower(module: nn.Module, example_chw=(1, 32, 32), train: bool = False) -> Plan:
+    """Record one forward of `module` on a CPU example [2, C, H, W] and turn it into a Plan: an eval forward with BatchNorm folded
+    away, or (``train=True``) a train-mode forward whose plan keeps every BatchNorm as a ``bn`` step on batch statistics and
+    names the module's live parameters and buffers by their state-dict keys instead of cloning them."""
+    m = copy.deepcopy(module).to("cpu").float()
+    m.train(train)
+    bn_of = _train_checks(m) if train else {}
     names = {}
     for n_, t in list(m.named_parameters()) + list(m.named_buffers()):
         names[id(t)] = n_
@@ -107,6 +131,7 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
     with torch.no_grad(), tape:
         y = m(x)
     plan = Plan()
+    plan.train = train
     vals: dict[int, Any] = {}         # id(tensor) -> Val | ("param", tensor) | ("paramT", tensor)
     plan.input = plan.new_buf(*example_chw)
     vals[id(x)] = plan.input
@@ -128,8 +153,12 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
 
     for func, args, kwargs, out in tape.entries:
         op = _opname(func)
+        if train and op in ("add", "add_") and id(args[0]) in names and not args[0].is_floating_point():
+            continue                                # num_batches_tracked += 1: the executor's bookkeeping
         if op in ("detach", "alias", "clone", "contiguous", "_to_copy", "dropout", "native_dropout"):
             src = args[0]
+            if train and op in ("dropout", "native_dropout"):
+                _need(not (args[1] > 0 and (len(args) < 3 or args[2] is None or args[2])), "live dropout (p > 0 in train() mode) has no kernel")
             vals[id(out if not isinstance(out, tuple) else out[0])] = get(src)
         elif op == "convolution":
             xin, w, b, stride, padding, dilation, transposed, _, groups = args[:9]
@@ -140,8 +169,26 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
             o = plan.new_buf(out.shape[1], out.shape[2], out.shape[3])
             plan.steps.append(Step("conv", o, [v], dict(w=w.detach().float(), b=None if b is None else b.detach().float(),
                                                         stride=s[0], pad=p_[0], groups=groups, relu=False, res=None,
-                                                        kh=w.shape[2], kw=w.shape[3])))
+                                                        kh=w.shape[2], kw=w.shape[3], wsrc=w, bsrc=b)))
             vals[id(out)] = o
+        elif train and op in ("_native_batch_norm_legit_no_training", "native_batch_norm", "cudnn_batch_norm", "_native_batch_norm_legit",
+                              "_native_batch_norm_legit_functional"):
+            xin, w, b, mean, var = args[:5]
+            _need(isinstance(mean, torch.Tensor) and id(mean) in bn_of, "BatchNorm without tracked running statistics is not served in train() mode")
+            _need(w is not None and b is not None and id(w) in names and id(b) in names, "BatchNorm(affine=False) is not served in train() mode")
+            mod = bn_of[id(mean)]
+            _need(mod.training, "a BatchNorm layer in eval() mode inside a train() module is not served")
+            v = get(xin)
+            _need(isinstance(v, Val), "shape / argument pattern not lowered")
+            o = plan.new_buf(v.C, v.H, v.W)
+            rm = names[id(mean)]
+            _need(all(s_.kind != "bn" or s_.p["rmname"] != rm for s_ in plan.steps),
+                  "a BatchNorm layer applied twice in one forward is not served in train() mode")   # (its d gamma / d beta would have to add up)
+            plan.steps.append(Step("bn", o, [v], dict(wname=names[id(w)], bname=names[id(b)], rmname=rm, rvname=names[id(var)],
+                                                      nbtname=rm[:-len("running_mean")] + "num_batches_tracked",
+                                                      eps=float(mod.eps), momentum=None if mod.momentum is None else float(mod.momentum),
+                                                      relu=False)))
+            vals[id(out[0])] = o
         elif op in ("_native_batch_norm_legit_no_training", "native_batch_norm", "cudnn_batch_norm",
                     "_native_batch_norm_legit"):
             xin, w, b, mean, var = args[:5]
@@ -257,17 +304,25 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
             o = plan.new_buf(w.shape[0], 1, 1)
             plan.steps.append(Step("conv", o, [v], dict(w=w.detach().float().reshape(w.shape[0], w.shape[1], 1, 1),
                                                         b=None if b is None else b.detach().float(), stride=1, pad=0,
-                                                        groups=1, relu=False, res=None, kh=1, kw=1)))
+                                                        groups=1, relu=False, res=None, kh=1, kw=1, wsrc=w, bsrc=b)))
             vals[id(out)] = o
-        elif op in ("size", "sym_size", "empty", "zeros", "ones", "zeros_like", "empty_like", "fill_", "copy_"):
+        elif op in ("size", "sym_size", "empty", "zeros", "ones", "zeros_like", "empty_like", "fill_", "copy_") or \
+                (train and op in ("_local_scalar_dense", "item")):   # (BatchNorm(momentum=None) reads num_batches_tracked)
             continue
         else:
             raise NotImplementedError(f"convnet lowering: ATen op '{op}' is not supported")
     plan.output = get(y)
     _need(isinstance(plan.output, Val), "shape / argument pattern not lowered")
-    _fuse(plan)
+    _fuse(plan, train)
     for st in plan.steps:
         if st.kind == "conv":
+            wsrc, bsrc = st.p.pop("wsrc"), st.p.pop("bsrc")
+            if train:                               # the module's live tensors, by name: nothing to go stale after optimizer.step()
+                _need(id(wsrc) in names and (bsrc is None or id(bsrc) in names), "a convolution whose weight is not a parameter of the module")
+                st.p.pop("w"), st.p.pop("b")
+                st.p["wname"], st.p["bname"] = names[id(wsrc)], None if bsrc is None else names[id(bsrc)]
+                st.p["wshape"] = (wsrc.shape[0], wsrc.shape[1], st.p["kh"], st.p["kw"])
+                continue
             st.p["wk"] = add_weight(st.p.pop("w"))
             b = st.p.pop("b")
             st.p["bk"] = None if b is None else add_weight(b)
@@ -281,9 +336,11 @@ def lower(module: nn.Module, example_chw=(1, 32, 32)) -> Plan:
     return plan
 
 
-def _fuse(plan: Plan):
+def _fuse(plan: Plan, train: bool = False):
     """conv -> BN (fold) -> ReLU, BN -> ReLU, add -> ReLU, conv (+ residual add) peepholes.  A producer is merged into
-    its consumer only when that consumer is the ONLY reader of the producer's buffer."""
+    its consumer only when that consumer is the ONLY reader of the producer's buffer.  A train plan folds nothing: BN -> ReLU sets
+    the ``bn`` step's flag, add -> ReLU and conv + residual add (a BatchNorm between them is a step of its own, so they are
+    not adjacent) stay, a ReLU straight after a conv stays a step."""
     def readers(buf):
         r = sum(1 for s in plan.steps for v in s.ins if v.buf == buf)
         return r + (1 if plan.output.buf == buf else 0)
@@ -298,14 +355,14 @@ def _fuse(plan: Plan):
             prod = next((s for s in plan.steps[:i] if s.out is not None and s.out.buf == src.buf and s.out.full), None)
             if st.kind == "affine" and prod is not None and src.full and readers(src.buf) == 1:
                 has_aff = st.p["scale"] is not None
-                if prod.kind == "conv" and not prod.p["relu"] and (prod.p["res"] is None or not has_aff):
+                if prod.kind == "conv" and not train and not prod.p["relu"] and (prod.p["res"] is None or not has_aff):
                     if has_aff:        # fold BN: w' = w * s, b' = b * s + t
                         s_, t_ = st.p["scale"], st.p["shift"]
                         prod.p["scale"] = s_ if prod.p.get("scale") is None else prod.p["scale"] * s_
                         b0 = prod.p["b"] if prod.p["b"] is not None else torch.zeros_like(t_)
                         prod.p["b"] = b0 * s_ + t_
                     prod.p["relu"] = st.p["relu"]
-                elif prod.kind in ("affine", "add") and not has_aff and not prod.p["relu"]:
+                elif prod.kind in ("affine", "add", "bn") and not has_aff and not prod.p["relu"]:
                     prod.p["relu"] = True
                 else:
                     continue
@@ -352,6 +409,50 @@ class _ConvNetInputGrad(torch.autograd.Function):
         return dx, None
 
 
+class _ConvNetTrainFn(torch.autograd.Function):
+    """Train-mode scores over (x, the module's parameters): the forward keeps every activation and each BatchNorm's batch
+    statistics, the backward runs the reverse sweep with ``bn`` steps and, per conv step, ap_conv2d_wgrad + ap_rowsum."""
+
+    @staticmethod
+    def forward(ctx, x, net, tplan, names, *params):
+        out, saved = net._run_train(x, tplan, keep=True)
+        ctx.net, ctx.tplan, ctx.names, ctx.saved = net, tplan, names, saved
+        ctx.save_for_backward(x, *params)                        # (an in-place change of x or a parameter before backward is torch's error;
+                                                                 #  the kept input activation may alias x)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():                              # create_graph=True reached this node
+            raise NotImplementedError("audiopure_amd NativeConvNet: no double backward through the train-mode step (create_graph=True)")
+        if ctx.saved is None:
+            raise RuntimeError("audiopure_amd NativeConvNet: the train-mode step was already back-propagated (its activations are freed)")
+        params = dict(zip(ctx.names, ctx.saved_tensors[1:]))
+        want = {n for n, need in zip(ctx.names, ctx.needs_input_grad[4:]) if need}
+        bufs, stats = ctx.saved
+        tr = _TrainSweep(ctx.tplan, params, stats, want, ctx.needs_input_grad[0])
+        with torch.no_grad():
+            dx = ctx.net._input_grad(bufs, g.detach().float().contiguous(), train=tr)
+        ctx.saved = None
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None) + tuple(tr.grads.get(n) for n in ctx.names)
+
+
+class _TrainSweep:
+    """What the reverse sweep needs beyond the activations when it runs a train plan: the live parameters by name, each ``bn``
+    step's [2][C] batch statistics, which parameters want a gradient, and where those gradients go."""
+
+    def __init__(self, plan, params, stats, want, want_dx):
+        self.plan, self.params, self.stats, self.want, self.want_dx = plan, params, stats, want, want_dx
+        self.grads = {}
+
+    def grad_of(self, name):
+        """-> (gradient tensor shaped like the parameter, accumulate flag): a parameter two steps share adds up."""
+        if name in self.grads:
+            return self.grads[name], 1
+        self.grads[name] = torch.empty_like(self.params[name], dtype=torch.float32)
+        return self.grads[name], 0
+
+
 def strict() -> bool:
     """``AUDIOPURE_STRICT=1``: the off-native routes of ``NativeConvNet.forward`` raise instead of running PyTorch operators."""
     import os
@@ -367,7 +468,9 @@ KNOWN_FAMILIES = frozenset({"VGG", "ResNet", "WideResNet", "CifarResNeXt", "DPN"
 
 class NativeConvNet(nn.Module):
     """``NativeConvNet(module)(x)`` == ``module.eval()(x)`` for the reference's 2-D classifiers, computed by the HIP
-    library.  The wrapped module keeps owning the parameters (``.module``); call ``refresh()`` after changing them."""
+    library.  The wrapped module keeps owning the parameters (``.module``); call ``refresh()`` after changing them.
+    In ``train()`` mode, with parameters and input on the device, ``forward`` is the module's train-mode forward (batch
+    statistics, running statistics updated in place) and its ``backward`` fills the parameters' gradients, both on the HIP library."""
 
     # class-level defaults: an instance restored without __init__ (copy / pickle of an older object) still works
     plan = None
@@ -388,7 +491,7 @@ class NativeConvNet(nn.Module):
 
     def __getstate__(self):                    # device images / packed weights are rebuilt on demand, never pickled
         d = dict(self.__dict__)
-        for k in ("_dev_weights", "_packed", "_dev", "_bwd_packed", "_bwd_key", "_zero_vec"):
+        for k in ("_dev_weights", "_packed", "_dev", "_bwd_packed", "_bwd_key", "_zero_vec", "_train_plan", "_train_chw", "_train_bufs"):
             d.pop(k, None)
         return d
 
@@ -404,8 +507,11 @@ class NativeConvNet(nn.Module):
         return self.module._get_name()
 
     def refresh(self):
+        """Re-lower after the wrapped module changed.  Also drops the train plan, which holds each BatchNorm's eps and momentum and
+        the decision that no dropout is live as they were when it was traced: change those on the module, then call this."""
         self.plan = lower(self.module, self.input_chw)
         self._dev_weights = None
+        self._train_plan, self._train_chw, self._train_bufs = None, None, None
 
     def _prepare(self, dev):
         lib = N.lib()
@@ -437,18 +543,27 @@ class NativeConvNet(nn.Module):
 
     def forward(self, x):
         """A module that ``lower_classifier`` wrapped on sight (``input_chw=None``) is only KNOWN to contain Conv2d layers.
-        What the reference's scripts would have done with it stays possible in three named cases -- ``train()`` mode (BatchNorm
-        statistics live: nothing to fold), a CPU module fed CPU tensors, and a trace that meets an operator the library has no
+        What the reference's scripts would have done with it stays possible in three named cases -- ``train()`` mode where the
+        train plan has no kernel (live dropout, ``affine=False``, ...) or the module is not on the device, a CPU module fed CPU tensors, and a trace that meets an operator the library has no
         kernel for (``lower`` raises ``NotImplementedError``; any other failure of the lowering propagates) -- each said once with
         a ``RuntimeWarning`` and each an error under ``AUDIOPURE_STRICT=1``.  An explicitly constructed
         ``NativeConvNet(module, chw)`` lowers in ``__init__`` and raises there instead."""
         if self.training and not self._foreign:
+            self.plan, self._dev_weights = None, None            # the eval plan holds weights folded at lowering: stale after a training step
+            if x.is_cuda and all(p.is_cuda for p in self.module.parameters()):
+                try:
+                    tplan = self._train_plan_for(x)
+                except NotImplementedError as e:                 # live dropout, affine=False, ...: no kernel -- today's announced route
+                    if strict():
+                        raise N.NativeError(f"{type(self.module).__name__}: train() mode not lowered ({e}); AUDIOPURE_STRICT=1 forbids "
+                                            "running the caller's module on PyTorch operators") from e
+                else:
+                    return self._forward_train(x, tplan)         # batch-statistics BatchNorm and parameter gradients on the HIP library
             if not getattr(self, "_warned_train", False):
                 import warnings
                 warnings.warn(f"{type(self.module).__name__}: train() mode -- the caller's module runs on PyTorch operators; the "
                               "native plan is re-lowered from the parameters at the next eval() forward", RuntimeWarning, stacklevel=2)
                 self._warned_train = True
-            self.plan, self._dev_weights = None, None            # the plan holds weights folded at lowering: stale after a training step
             return self._off_native(x, "train() mode")
         if self._foreign:
             return self._off_native(x, "not lowered (an operator without a kernel)")
@@ -534,6 +649,129 @@ class NativeConvNet(nn.Module):
         assert o.full
         return (out.view(B, -1) if (o.H == 1 and o.W == 1) else out), bufs
 
+    # ---- train() mode: batch-statistics BatchNorm, parameter gradients (train_speech_commands.py:122-153) ---------
+    _train_plan = None
+    _train_chw = None
+    _train_bufs = None                         # per conv step: the packed forward / backward weight images, written anew every step
+
+    def _train_plan_for(self, x):
+        if x.dim() != 4:
+            raise ValueError(f"expected [B, C, H, W], got {tuple(x.shape)}")
+        chw = tuple(x.shape[1:])
+        if self._train_plan is None or self._train_chw != chw:
+            self._train_plan, self._train_chw, self._train_bufs = lower(self.module, chw, train=True), chw, None
+        return self._train_plan
+
+    def _live_tensors(self):
+        d = dict(self.module.named_parameters())
+        d.update(self.module.named_buffers())
+        return d
+
+    @N.on_device
+    def _forward_train(self, x, tplan):
+        if self._conv_flags:
+            raise N.NativeError("NativeConvNet: train() mode runs in 'f32' only; set_precision('f32') before training")
+        live = self._live_tensors()
+        pnames = tuple(n for n, _ in self.module.named_parameters())
+        if any(live[n].dtype != torch.float32 or not live[n].is_contiguous() for n in pnames):
+            raise N.NativeError("NativeConvNet: train() mode needs contiguous float32 parameters")
+        if torch.is_grad_enabled() and (x.requires_grad or any(live[n].requires_grad for n in pnames)):
+            return _ConvNetTrainFn.apply(x, self, tplan, pnames, *[live[n] for n in pnames])
+        return self._run_train(x, tplan, keep=False)[0]          # no_grad: the statistics move, nothing is kept
+
+    def _train_images(self, tplan, dev):
+        """Device buffers for the packed weight images of every conv step (forward and transposed), the flip scratch and the
+        BatchNorm workspace: allocated once per train plan, rewritten from the live weights at every step."""
+        if self._train_bufs is not None and self._train_bufs["dev"] == dev:
+            return self._train_bufs
+        lib = N.lib()
+        f32 = dict(device=dev, dtype=torch.float32)
+        fwd, bwd, wmax, cmax = {}, {}, 1, 1
+        for i, st in enumerate(tplan.steps):
+            if st.kind == "conv":
+                Cout, Cg, kh, kw = st.p["wshape"]
+                g = st.p["groups"]
+                fwd[i] = torch.empty(lib.ap_conv2d_packed_elems(Cout, Cg, kh, kw, g), **f32)
+                bwd[i] = torch.empty(lib.ap_conv2d_packed_elems(g * Cg, Cout // g, kh, kw, g), **f32)
+                wmax = max(wmax, Cout * Cg * kh * kw)
+            elif st.kind == "bn":
+                cmax = max(cmax, st.out.C)
+        self._train_bufs = dict(dev=dev, fwd=fwd, bwd=bwd, flip=torch.empty(wmax, **f32),
+                                bn_ws=torch.empty(lib.ap_bn2d_train_workspace_bytes(cmax), device=dev, dtype=torch.uint8))
+        return self._train_bufs
+
+    def _run_train(self, x, tplan, keep):
+        """-> (scores, (every buffer of the plan, {bn step: its [2][C] batch statistics}) or None).  Updates running_mean /
+        running_var in place (the kernels do) and increments num_batches_tracked, as nn.BatchNorm2d does (also under no_grad).  The
+        counters are int64 bookkeeping and move by one fused torch call per step, the only torch operator in it; a
+        BatchNorm(momentum=None) additionally reads its counter on the host (one device-to-host copy per such layer and step), as
+        torch's own module does."""
+        if tuple(x.shape[1:]) != self._train_chw:
+            raise ValueError(f"expected [B, {self._train_chw}], got {tuple(x.shape)}")
+        dev = x.device
+        N.use_conv_workspace(dev)
+        lib, st_, B = N.lib(), N.stream(), x.shape[0]
+        live, img = self._live_tensors(), self._train_images(tplan, dev)
+        bufs = {tplan.input.buf: x.detach().float().contiguous()}
+        stats, counters = {}, []
+        ws, ws_bytes = img["bn_ws"].data_ptr(), img["bn_ws"].numel()
+
+        def buf(v):
+            if v.buf not in bufs:
+                C_, H_, W_ = tplan.buf_shape[v.buf]
+                bufs[v.buf] = torch.empty((B, C_, H_, W_), device=dev, dtype=torch.float32)
+            return bufs[v.buf]
+
+        for i, s in enumerate(tplan.steps):
+            o, p = s.out, s.p
+            ob = buf(o)
+            if s.kind == "conv":
+                v = s.ins[0]
+                assert o.full and not p["relu"]
+                Cout, Cg, kh, kw = p["wshape"]
+                N.check(lib.ap_conv2d_pack(N.ptr(live[p["wname"]].detach()), None, N.ptr(img["fwd"][i]), Cout, Cg, kh, kw, p["groups"], st_),
+                        "ap_conv2d_pack")
+                res = N.ptr(buf(p["res"])) if p["res"] is not None else None
+                N.check(lib.ap_conv2d_fwd(N.ptr(buf(v)), N.ptr(img["fwd"][i]), N.ptr(live[p["bname"]].detach()) if p["bname"] else None, res,
+                                          N.ptr(ob), B, v.C, v.H, v.W, o.C, kh, kw, p["stride"], p["pad"], p["groups"], 0, v.cstride,
+                                          v.coff, st_), "ap_conv2d_fwd")
+            elif s.kind == "bn":
+                v = s.ins[0]
+                assert o.full
+                nbt = live.get(p["nbtname"])
+                mom = p["momentum"] if p["momentum"] is not None else 1.0 / (int(nbt) + 1)   # momentum=None: the cumulative average
+                stat = torch.empty((2, o.C), device=dev, dtype=torch.float32)
+                N.check(lib.ap_bn2d_train_fwd(N.ptr(buf(v)), N.ptr(live[p["wname"]].detach()), N.ptr(live[p["bname"]].detach()),
+                                              N.ptr(live[p["rmname"]]), N.ptr(live[p["rvname"]]), N.ptr(ob), N.ptr(stat), ws, ws_bytes,
+                                              B, o.C, o.H * o.W, v.cstride, v.coff, p["eps"], mom, int(p["relu"]), st_), "ap_bn2d_train_fwd")
+                if nbt is not None:
+                    counters.append(nbt)
+                stats[i] = stat
+            elif s.kind == "affine":
+                v = s.ins[0]
+                assert o.full and p["sk"] is None
+                N.check(lib.ap_affine_nchw(N.ptr(buf(v)), None, None, N.ptr(ob), B, v.C, v.H * v.W, v.cstride, v.coff, int(p["relu"]), st_),
+                        "ap_affine_nchw")
+            elif s.kind == "add":
+                a, b = s.ins
+                assert o.full
+                N.check(lib.ap_add_nchw(N.ptr(buf(a)), N.ptr(buf(b)), N.ptr(ob), B, a.C, a.H * a.W, a.cstride, a.coff,
+                                        b.cstride, b.coff, int(p["relu"]), st_), "ap_add_nchw")
+            elif s.kind == "copy":
+                v = s.ins[0]
+                N.check(lib.ap_copy_channels(N.ptr(buf(v)), N.ptr(ob), B, v.C, v.H * v.W, v.cstride, v.coff, o.cstride,
+                                             o.coff, st_), "ap_copy_channels")
+            elif s.kind == "pool":
+                v = s.ins[0]
+                N.check(lib.ap_pool2d(N.ptr(buf(v)), N.ptr(ob), B * v.C, v.H, v.W, p["k"], p["stride"], p["pad"],
+                                      int(p["is_max"]), st_), "ap_pool2d")
+        if counters:                                             # num_batches_tracked += 1, every BatchNorm's int64 counter in one
+            torch._foreach_add_(counters, 1)                     # fused torch call: the step's only torch operator
+        o = tplan.output
+        out = buf(o)
+        assert o.full
+        return (out.view(B, -1) if (o.H == 1 and o.W == 1) else out), ((bufs, stats) if keep else None)
+
     # ---- input gradient (SURVEY section 8 f-1 for the spectrogram classifiers) ------------------------------------
     def _prepare_backward(self):
         """Per conv step: the flipped, transposed weights (BatchNorm scale folded in) packed for ap_conv2d_fwd."""
@@ -555,17 +793,26 @@ class NativeConvNet(nn.Module):
         torch.cuda.synchronize(dev)
         self._bwd_packed = packs
 
-    def _input_grad(self, bufs, dout, keep=None):
+    def _input_grad(self, bufs, dout, keep=None, train=None):
         """Reverse sweep over the plan: every step adds its contribution into the gradient buffers of its inputs.
         ``keep``: a dict that receives every gradient buffer of the sweep ({buf id: [B, C, H, W]}, the layout of ``bufs``) -- for
-        tests that check the sweep step by step; the arithmetic does not depend on it."""
-        if getattr(self, "_bwd_packed", None) is None or self._bwd_key is not self._dev_weights:
+        tests that check the sweep step by step; the arithmetic does not depend on it.
+        ``train`` (a ``_TrainSweep``): the sweep runs that train plan instead -- ``bn`` steps go through ap_bn2d_train_bwd, every conv
+        step packs its transposed image from the live weight (ap_conv2d_pack_bwd) and leaves dW (ap_conv2d_wgrad) and db (ap_rowsum) in
+        ``train.grads`` for the parameters that want one."""
+        if train is None and (getattr(self, "_bwd_packed", None) is None or self._bwd_key is not self._dev_weights):
             self._prepare_backward()
             self._bwd_key = self._dev_weights
         lib, W, st_ = N.lib(), self._dev_weights, N.stream()
-        plan = self.plan
+        plan = self.plan if train is None else train.plan
         B, dev = dout.shape[0], dout.device
         grads = {}
+        if train is not None:
+            img = self._train_images(plan, dev)
+            wg_bytes = max([lib.ap_conv2d_wgrad_workspace_bytes(B, s.ins[0].C, s.ins[0].H, s.ins[0].W, s.out.C, s.p["kh"], s.p["kw"],
+                                                                s.p["stride"], s.p["pad"], s.p["groups"])
+                            for s in plan.steps if s.kind == "conv" and s.p["wname"] in train.want] + [0])
+            wg_ws = torch.empty(max(wg_bytes, 4), device=dev, dtype=torch.uint8)
 
         def gbuf(b):
             if b not in grads:
@@ -599,6 +846,21 @@ class NativeConvNet(nn.Module):
                     acc(dy, o.C, o.H * o.W, o.C, 0, p["res"])
                 k, sd, pad = p["kh"], p["stride"], p["pad"]
                 assert p["kh"] == p["kw"] and pad <= k - 1
+                packed = None if train is not None else self._bwd_packed[i]
+                if train is not None:
+                    if p["wname"] in train.want:
+                        dW, accum = train.grad_of(p["wname"])
+                        N.check(lib.ap_conv2d_wgrad(N.ptr(dy), N.ptr(bufs[v.buf]), N.ptr(dW), wg_ws.data_ptr(), wg_ws.numel(), B, v.C, v.H,
+                                                    v.W, o.C, k, k, sd, pad, p["groups"], v.cstride, v.coff, accum, st_), "ap_conv2d_wgrad")
+                    if p["bname"] in train.want:
+                        db, accum = train.grad_of(p["bname"])
+                        N.check(lib.ap_rowsum(N.ptr(dy), None, None, N.ptr(db), B, o.C, o.H * o.W, 0, 1.0, accum, st_), "ap_rowsum")
+                    if v.buf == plan.input.buf and not train.want_dx:
+                        continue                                 # the first layer: nobody asked for dx
+                    Cout, Cg, _, _ = p["wshape"]
+                    packed = img["bwd"][i]
+                    N.check(lib.ap_conv2d_pack_bwd(N.ptr(train.params[p["wname"]].detach()), N.ptr(packed), N.ptr(img["flip"]), Cout, Cg, k,
+                                                   k, p["groups"], st_), "ap_conv2d_pack_bwd")
                 src, Hs, Ws = dy, o.H, o.W
                 if sd > 1:
                     Hs = (o.H - 1) * sd + 1 + (v.H + 2 * pad - k) % sd
@@ -607,9 +869,22 @@ class NativeConvNet(nn.Module):
                     N.check(lib.ap_zero_insert2d(N.ptr(dy), N.ptr(src), B * o.C, o.H, o.W, Hs, Ws, sd, st_), "ap_zero_insert2d")
                 tmp = torch.empty((B, v.C, v.H, v.W), device=dev, dtype=torch.float32)
                 assert Hs + 2 * (k - 1 - pad) - k + 1 == v.H and Ws + 2 * (k - 1 - pad) - k + 1 == v.W
-                N.check(lib.ap_conv2d_fwd(N.ptr(src), N.ptr(self._bwd_packed[i]), None, None, N.ptr(tmp), B, o.C, Hs, Ws, v.C, k, k,
+                N.check(lib.ap_conv2d_fwd(N.ptr(src), N.ptr(packed), None, None, N.ptr(tmp), B, o.C, Hs, Ws, v.C, k, k,
                                           1, k - 1 - pad, p["groups"], self._conv_flags, o.C, 0, st_), "ap_conv2d_fwd")
                 acc(tmp, v.C, v.H * v.W, v.C, 0, v)
+            elif s.kind == "bn":
+                v = s.ins[0]
+                assert o.full
+                dg = train.grad_of(p["wname"])[0] if p["wname"] in train.want else None
+                db = train.grad_of(p["bname"])[0] if p["bname"] in train.want else None
+                want = v.buf != plan.input.buf or train.want_dx  # a BatchNorm on the input itself: dx only if somebody asked
+                tmp = torch.empty((B, o.C, o.H, o.W), device=dev, dtype=torch.float32) if want else None
+                N.check(lib.ap_bn2d_train_bwd(N.ptr(bufs[v.buf]), N.ptr(bufs[o.buf]), N.ptr(gbuf(o.buf)), N.ptr(train.params[p["wname"]].detach()),
+                                              N.ptr(train.stats[i]), N.ptr(tmp), N.ptr(dg), N.ptr(db), img["bn_ws"].data_ptr(),
+                                              img["bn_ws"].numel(), B, o.C, o.H * o.W, v.cstride, v.coff, int(p["relu"]), st_),
+                        "ap_bn2d_train_bwd")
+                if want:
+                    acc(tmp, o.C, o.H * o.W, o.C, 0, v)
             elif s.kind == "affine":
                 v = s.ins[0]
                 dy = masked(o, p["relu"])

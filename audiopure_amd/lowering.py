@@ -9,8 +9,9 @@ kws_adaptive_attack_eval.py:64-66), so "scripts unchanged" means those objects a
 * a module called ``KWSModel`` with ``CRNN_model / attn_layer / apply_attn`` (RCNN_KWS/model.py:66-90) -> native ``KWSModel``
 * any other module that contains ``nn.Conv2d`` layers (VGG / ResNet / WRN / ResNeXt / DPN / DenseNet pickles)
                                                                                               -> ``NativeConvNet(module)``
-  (lowered at its first input; a module whose trace meets an operator without a kernel, one left in ``train()`` mode, or a
-  CPU module given CPU input keeps running as the caller built it -- ``NativeConvNet.forward`` says so once)
+  (lowered at its first input; in ``train()`` mode on the device it runs the native training step; a module whose trace meets
+  an operator without a kernel -- live dropout in ``train()`` mode among them -- or a CPU module given CPU input keeps running as
+  the caller built it -- ``NativeConvNet.forward`` says so once)
 * ``Compose([MelSpectrogram(n_fft=2048, hop_length=512, n_mels, norm='slaney', pad_mode='constant',
   mel_scale='slaney'), AmplitudeToDB('power')])``                                             -> ``MelSpecDB(n_mels)``
 * ``Sequential(MelSpectrogram(sample_rate=16000, n_mels), AmplitudeToDB('power'))`` (torchaudio defaults: n_fft 400,

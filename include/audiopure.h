@@ -635,6 +635,43 @@ int ap_m5_train_fwd(ap_m5 *m, const float *blob, const float *x, float *logprobs
 int ap_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float *dlogprobs, float *grads, float *dx, void *workspace,
                     size_t ws_bytes, int B, int L, void *stream);
 
+/* ---- train-mode step of the 2-D ConvNet classifiers (ap_convnet_train.hip).  The reference trains them with
+ * audio_models/ConvNets_SpeechCommands/train_speech_commands.py:122-153 (model.train(), criterion(model(x), y), loss.backward(),
+ * optimizer.step(); adv_train_speech_commands.py:191-225 likewise); its autograd forms what these entry points form.  Conv forward and
+ * conv dx stay ap_conv2d_fwd, the biases ap_rowsum.  No floating-point atomics: every sum has a fixed order and a slice count that is a
+ * constant, two runs give equal bits.  A launch allocates nothing; every refusal is -22 with ap_last_error set before any launch. ---- */
+/* nn.Conv2d / nn.Linear weight gradient (the autograd of F.conv2d in models/resnext.py:39-51, resnet.py:84-103, wideresnet.py:28-41,
+ * dpn.py:35-45, densenet.py:36-44 and of the classifiers' nn.Linear):
+ *   dW[Cout][Cin/g][k][k] (+)= sum_{b,oh,ow} dy[b][m][oh][ow] x[b][g Cin/g + n][oh s + i - pad][ow s + j - pad], terms outside the image 0;
+ * x = channels [x_coff, x_coff + Cin) of a tensor of x_cstride channels, dy [B][Cout][OH][OW] with OH = (H + 2 pad - k) / s + 1.
+ * Square k in {1, 3, 7}, stride 1 or 2, 0 <= pad <= k - 1, groups dividing both channel counts; Cin = 1 and H = W = 1 (nn.Linear) are
+ * ordinary cases.  Implicit GEMM on v_mfma_f32_32x32x2_f32 (per group rows Cout/g, columns (Cin/g) k k, contraction B OH OW), the
+ * contraction split over workgroups into `workspace` (ap_conv2d_wgrad_workspace_bytes, 0 where the shape is refused) and added in
+ * slice order by a second kernel. */
+size_t ap_conv2d_wgrad_workspace_bytes(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups);
+int ap_conv2d_wgrad(const float *dy, const float *x, float *dW, void *workspace, size_t ws_bytes, int B, int Cin, int H, int W, int Cout,
+                    int kh, int kw, int stride, int pad, int groups, int x_cstride, int x_coff, int accumulate, void *stream);
+/* The A-operand image ap_conv2d_fwd reads for the conv's input gradient (the transposed convolution autograd runs for the same
+ * F.conv2d calls), from the LIVE weight w [Cout][Cin/g][k][k]: taps flipped, in / out swapped within each group, i.e. ap_conv2d_pack of
+ * wt[g Cin/g + n][m][i][j] = w[g Cout/g + m][n][k-1-i][k-1-j].  wT: ap_conv2d_packed_elems(groups Cin/g, Cout/g, k, k, groups) floats;
+ * scratch: Cout Cin/g k k floats (receives wt). */
+int ap_conv2d_pack_bwd(const float *w, float *wT, float *scratch, int Cout, int Cin_g, int kh, int kw, int groups, void *stream);
+/* nn.BatchNorm2d in training mode (F.batch_norm(training=True) of the same model files, e.g. models/resnext.py:40-50) on x = channels
+ * [x_coff, x_coff + C) of [B][x_cstride][HW].  Forward: per channel the mean and the biased variance over n = B HW values from 64 fixed
+ * slices summed in fp64; y [B][C][HW] = gamma xhat + beta, ReLU'd if relu != 0; stat [2][C] = mean, 1 / sqrt(var + eps);
+ * running_mean / running_var updated in place as (1 - momentum) old + momentum batch, the variance unbiased (n / (n - 1)).
+ * Backward (y: the forward's output, read only when relu != 0; stat: the forward's): dy' = dy where y > 0 (all of dy without the ReLU),
+ *   dbeta = sum dy', dgamma = sum dy' xhat, dx [B][C][HW] = gamma rstd (dy' - mean(dy') - xhat mean(dy' xhat));
+ * dx, dgamma, dbeta may each be NULL.  gamma of either sign or 0 is served; n <= 1 is refused (torch raises there too).
+ * workspace: ap_bn2d_train_workspace_bytes(C) bytes, 8-byte aligned. */
+size_t ap_bn2d_train_workspace_bytes(int C);
+int ap_bn2d_train_fwd(const float *x, const float *gamma, const float *beta, float *running_mean, float *running_var, float *y,
+                      float *stat, void *workspace, size_t ws_bytes, int B, int C, int HW, int x_cstride, int x_coff, float eps,
+                      float momentum, int relu, void *stream);
+int ap_bn2d_train_bwd(const float *x, const float *y, const float *dy, const float *gamma, const float *stat, float *dx, float *dgamma,
+                      float *dbeta, void *workspace, size_t ws_bytes, int B, int C, int HW, int x_cstride, int x_coff, int relu,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
