@@ -162,6 +162,11 @@ SIGNATURES = {
     "ap_bn2d_train_workspace_bytes": (_sz, [_i]),
     "ap_bn2d_train_fwd": (_i, [_fp] * 7 + [_vp, _sz, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "ap_bn2d_train_bwd": (_i, [_fp] * 8 + [_vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
+    "ap_groupnorm_train_workspace_bytes": (_sz, [_i, _i]),
+    "ap_groupnorm_train_bwd": (_i, [_fp] * 9 + [_vp, _sz, _i, _i, _i, _i, _f, _i, _vp]),
+    "ap_dropout": (_i, [_fp, _fp, _i, _i, _f, _u64, _u32, _u64, _vp]),
+    "ap_silu_bwd": (_i, [_fp, _fp, _fp, _sz, _vp]),
+    "ap_qsample_rows": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
 }
 
 _LIB = None

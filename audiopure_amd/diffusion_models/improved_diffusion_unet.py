@@ -6,6 +6,8 @@ GroupNorm32 fused with the scale-shift FiLM and SiLU, QKV attention, nearest up-
 
 The modules below only HOLD parameters under the reference's names (``input_blocks.4.0.in_layers.2.weight`` ...), so a
 reference checkpoint (``model*.pt`` / ``ema_*.pt`` bare state dicts, train_util.py:274-297) loads unchanged.
+``forward_train`` is the train-mode network (live dropout, every parameter gradient from HIP kernels: ap_unet_train.hip,
+ap_conv2d_wgrad); ``improved_diffusion_train.training_losses`` wraps it in the reference's loss.
 Not built (raises): class conditioning, ``use_scale_shift_norm=False``, ``conv_resample=False``, dims != 2.
 """
 from __future__ import annotations
@@ -56,10 +58,12 @@ class UNetModel(nn.Module):
     _key = None
     _tape = None
     _conv_flags = 0
+    _train = None                              # the state of one forward_train evaluation (dropout seed, draw counter)
+    dropout_p = 0.0                            # nn.Dropout's p of the ResBlocks (unet.py:150-160); class default: old pickles load
 
     def __getstate__(self):                    # packed device images and the tape are rebuilt on demand, never pickled
         d = dict(self.__dict__)
-        for k in ("_packed", "_key", "_tape"):
+        for k in ("_packed", "_key", "_tape", "_train"):
             d.pop(k, None)
         d["_packed_t"] = {}
         return d
@@ -76,6 +80,7 @@ class UNetModel(nn.Module):
             num_heads_upsample = num_heads
         self.in_channels, self.model_channels, self.out_channels = in_channels, model_channels, out_channels
         self.num_heads, self.num_heads_upsample = num_heads, num_heads_upsample
+        self.dropout_p = float(dropout)        # applied by forward_train only (ap_dropout); the holders' nn.Dropout stays inert
         ted = model_channels * 4
         self.time_embed = nn.Sequential(nn.Linear(model_channels, ted), nn.SiLU(), nn.Linear(ted, ted))
         self.input_blocks = nn.ModuleList([nn.Sequential(nn.Conv2d(in_channels, model_channels, 3, padding=1))])
@@ -188,9 +193,24 @@ class UNetModel(nn.Module):
         off, n = self._emb_rows[rb]                                                                 # :182: this block's rows of the
         ss = torch.empty((B, n), device=x.device, dtype=torch.float32)                              # one projection of the step
         N.check(N.lib().ap_copy_channels(N.ptr(emb_proj), N.ptr(ss), B, n, 1, emb_proj.shape[1], off, n, 0, N.stream()))
+        if self._train is not None:
+            self._tape.append(("ss", ss, off, n))
         h = self._gn(rb.out_layers[0], h, ss=ss)                                                   # :186-190 (+ SiLU)
+        if self._train is not None:                                                                 # :150-160 nn.Dropout(p)
+            h = self._dropout(h)
         skip = x if isinstance(rb.skip_connection, nn.Identity) else self._conv(rb.skip_connection, x, B, C_, H, W)
         return self._conv(rb.out_layers[3], h, B, rb.out_channels, H, W, res=skip, dest=dest)      # :194
+
+    def _dropout(self, h):
+        tr = self._train
+        draw, tr["draw"] = tr["draw"], tr["draw"] + 1          # the ResBlock's ordinal in execution order, launched or not
+        if tr["p"] == 0.0:
+            return h
+        y = torch.empty_like(h)
+        N.check(N.lib().ap_dropout(N.ptr(h), N.ptr(y), h.shape[0], h[0].numel(), tr["p"], tr["seed"], draw, tr["offset"], N.stream()),
+                "ap_dropout")
+        self._tape.append(("drop", h, y, draw))
+        return y
 
     def _attention(self, ab, x, dest=None):
         B, C_, H, W = x.shape
@@ -272,16 +292,25 @@ class UNetModel(nn.Module):
             t = t.expand(B).contiguous()
         temb = torch.empty((B, self.model_channels), device=dev, dtype=torch.float32)
         N.check(lib.ap_timestep_embedding(N.ptr(t), N.ptr(self._freqs), N.ptr(temb), B, self.model_channels, N.stream()))
-        e = self._conv(self.time_embed[0], temb, B, self.model_channels, 1, 1, track=False).view(B, -1)
+        train = self._train is not None                                     # forward_train also records the embedding path
+        e4 = self._conv(self.time_embed[0], temb, B, self.model_channels, 1, 1, track=train)
+        e = e4.view(B, -1)
         e_s = torch.empty_like(e)
         N.check(lib.ap_silu(N.ptr(e), N.ptr(e_s), e.numel(), N.stream()))
-        emb = self._conv(self.time_embed[2], e_s, B, e.shape[1], 1, 1, track=False).view(B, -1)    # unet.py:479
+        if train:                                                           # (records stand in execution order: the sweep reverses it)
+            self._tape += [("notgrad", temb), ("silu", e4, e_s)]
+        emb4 = self._conv(self.time_embed[2], e_s, B, e.shape[1], 1, 1, track=train)               # unet.py:479
+        emb = emb4.view(B, -1)
         emb_s = torch.empty_like(emb)                                      # every ResBlock starts emb_layers with SiLU
         N.check(lib.ap_silu(N.ptr(emb), N.ptr(emb_s), emb.numel(), N.stream()))
+        if train:
+            self._tape.append(("silu", emb4, emb_s))
         wT, bcat, total = self._emb_cat                                    # all blocks' emb_layers Linear in one GEMM: [B, total]
         emb_proj = torch.empty((B, total), device=dev, dtype=torch.float32)
         N.check(lib.ap_conv2d_fwd(N.ptr(emb_s), N.ptr(wT), N.ptr(bcat), None, N.ptr(emb_proj), B, emb.shape[1], 1, 1, total, 1, 1, 1,
                                   0, 1, getattr(self, "_conv_flags", 0), emb.shape[1], 0, N.stream()), "ap_conv2d_fwd")
+        if train:
+            self._tape.append(("embcat", emb_s, emb_proj))
         hs, h = [], x
         for blk in self.input_blocks:                                       # :486-488
             h = self._run(blk, h, emb_proj)
@@ -323,6 +352,8 @@ class UNetModel(nn.Module):
         """Packed image of the transposed convolution of ``m`` (spatially flipped, in/out swapped)."""
         if m not in self._packed_t:
             w = m.weight.detach().float()
+            if w.dim() == 2:                                      # nn.Linear (forward_train's embedding path)
+                w = w[..., None, None]
             if w.dim() == 3:
                 w = w[..., None]
             wt = w.flip(2, 3).permute(1, 0, 2, 3).contiguous()
@@ -413,6 +444,256 @@ class UNetModel(nn.Module):
             elif kind == "in":
                 return grads[id(op[1])]
         raise RuntimeError("tape without an input record")
+
+    # ---- training step: eps on an autograd node over (x, every parameter) --------------------------------------------
+    def _dropout_config(self, dropout):
+        """``None`` | ("philox", seed, sample_offset[, p]) -> dict(p, seed, offset, draw)."""
+        if dropout is None:
+            w = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)          # torch's CPU generator: torch.manual_seed reproduces a step
+            seed, offset, p = (int(w[0]) << 32) | int(w[1]), 0, self.dropout_p
+        else:
+            if not (isinstance(dropout, (tuple, list)) and len(dropout) in (3, 4) and dropout[0] == "philox"):
+                raise ValueError('dropout: None, ("philox", seed, sample_offset) or ("philox", seed, sample_offset, p)')
+            seed, offset = int(dropout[1]) & ((1 << 64) - 1), int(dropout[2])
+            p = float(dropout[3]) if len(dropout) == 4 else self.dropout_p
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"dropout p = {p} outside [0, 1)")
+        return dict(p=p, seed=seed, offset=offset, draw=0)
+
+    @N.on_device
+    def forward_train(self, x, timesteps, dropout=None):
+        """eps of the train-mode network (nn.Dropout(p) live behind every ResBlock's FiLM-ed GroupNorm, unet.py:150-160,186-190) on an
+        autograd node over x and every parameter: ``loss.backward()`` leaves ``.grad`` on the parameters that require it (and dx if
+        x requires grad), all from HIP kernels.  fp32 arithmetic only."""
+        if getattr(self, "_conv_flags", 0) != 0:
+            raise N.NativeError('audiopure_amd UNetModel.forward_train runs in fp32 only: set_precision("f32")')
+        cfg = self._dropout_config(dropout)
+        names, params = zip(*self.named_parameters())
+        return _UNetTrainFn.apply(x, self, timesteps, cfg, *params)
+
+    def _forward_train(self, x, timesteps, cfg):
+        self._tape, self._train = [], cfg
+        try:
+            out = self._forward(x, timesteps)
+            return out, self._tape
+        finally:
+            self._tape, self._train = None, None
+
+    def _emb_cat_t(self):
+        """Packed image of the transposed concatenated emb_layers projection (its Linear input gradient)."""
+        if "embcat" not in self._packed_t:
+            rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
+            wt = torch.cat([rb.emb_layers[1].weight.detach().float() for rb in rbs], 0).t().contiguous()[..., None, None]
+            co, ci = wt.shape[0], wt.shape[1]
+            img = torch.empty(N.lib().ap_conv2d_packed_elems(co, ci, 1, 1, 1), device=wt.device, dtype=torch.float32)
+            N.check(N.lib().ap_conv2d_pack(N.ptr(wt.contiguous()), None, N.ptr(img), co, ci, 1, 1, 1, N.stream()), "ap_conv2d_pack")
+            self._packed_t["embcat"] = img
+        return self._packed_t["embcat"]
+
+    def _train_grad(self, tape, dout, want, want_dx, cfg):
+        """The reverse sweep of ``input_grad`` with every parameter cotangent: per conv op dW (ap_conv2d_wgrad) and db (ap_rowsum) from
+        the live weights' taped activations, per gn op ap_groupnorm_train_bwd, per dropout op ap_dropout on the cotangent, the FiLM
+        cotangents gathered into one [B][total] row block for the concatenated emb_layers GEMM, then the time_embed path.
+        ``want``: {parameter: bool}.  -> (dx or None, {parameter: gradient})."""
+        lib, st = N.lib(), N.stream
+        self._prepare()                                           # the transposed images belong to the weights the forward read
+        dev = dout.device
+        out_t = tape[-1][4]
+        B = out_t.shape[0]
+        grads = {id(out_t): dout.detach().float().contiguous()}
+        pgrad = {}
+        x_in = next(op[1] for op in tape if op[0] == "in")
+        no_dx = {id(op[1]) for op in tape if op[0] == "notgrad"}
+        if not want_dx:
+            no_dx.add(id(x_in))
+        emb_s, emb_proj = next((op[1], op[2]) for op in tape if op[0] == "embcat")
+        total, ted = emb_proj.shape[1], emb_s.shape[1]
+        rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
+
+        # one workspace per kind, sized to the largest op of this tape (torch's allocator; the launches allocate nothing)
+        wg = [lib.ap_conv2d_wgrad_workspace_bytes(B, ted, 1, 1, total, 1, 1, 1, 0, 1)]
+        gnb = [0]
+        for op in tape:
+            if op[0] == "conv" and want[op[1].weight]:
+                _, m, _, _, _, (_, Cin, H, W) = op
+                _, _, cout, kh, kw, stride, pad = self._packed[m]
+                nb = lib.ap_conv2d_wgrad_workspace_bytes(B, Cin, H, W, cout, kh, kw, stride, pad, 1)
+                if nb == 0:
+                    raise N.NativeError(f"ap_conv2d_wgrad refuses {type(m).__name__} {tuple(m.weight.shape)}: "
+                                        f"{(lib.ap_last_error() or b'').decode(errors='replace')}")
+                wg.append(nb)
+            elif op[0] == "gn":
+                gnb.append(lib.ap_groupnorm_train_workspace_bytes(B, op[2].shape[1]))
+        wg_ws = torch.empty(max(wg), device=dev, dtype=torch.uint8)
+        gn_ws = torch.empty(max(max(gnb), 4), device=dev, dtype=torch.uint8)
+
+        def acc(t, g):
+            k = id(t)
+            if k in grads:
+                N.check(lib.ap_axpbyc(N.ptr(grads[k]), N.ptr(g), N.ptr(grads[k]), 1.0, 1.0, 0.0, g.numel(), st()), "ap_axpbyc")
+            else:
+                grads[k] = g
+
+        def wgrad(dy, xa, w, bias, Cin, H, W, cout, k, stride, pad, L):
+            if w is not None:
+                dW = torch.empty(w, device=dev, dtype=torch.float32)
+                N.check(lib.ap_conv2d_wgrad(N.ptr(dy), N.ptr(xa), N.ptr(dW), wg_ws.data_ptr(), wg_ws.numel(), B, Cin, H, W, cout, k, k,
+                                            stride, pad, 1, Cin, 0, 0, st()), "ap_conv2d_wgrad")
+            else:
+                dW = None
+            if bias:
+                db = torch.empty(cout, device=dev, dtype=torch.float32)
+                N.check(lib.ap_rowsum(N.ptr(dy), None, None, N.ptr(db), B, cout, L, 0, 1.0, 0, st()), "ap_rowsum")
+            else:
+                db = None
+            return dW, db
+
+        for op in reversed(tape):
+            kind = op[0]
+            if kind == "conv":
+                _, m, x, res, out, (_, Cin, H, W) = op
+                g = grads.pop(id(out), None)
+                if g is None:
+                    continue
+                _, _, cout, kh, kw, stride, pad = self._packed[m]
+                Ho, Wo = out.shape[2], out.shape[3]
+                dW, db = wgrad(g, x, tuple(m.weight.shape) if want[m.weight] else None, m.bias is not None and want[m.bias],
+                               Cin, H, W, cout, kh, stride, pad, Ho * Wo)
+                if dW is not None:
+                    pgrad[m.weight] = dW
+                if db is not None:
+                    pgrad[m.bias] = db
+                if id(x) not in no_dx:
+                    if stride != 1:                               # Downsample: spread dy onto the input grid first
+                        z = torch.empty((B, cout, H, W), device=dev, dtype=torch.float32)
+                        N.check(lib.ap_zero_insert2d(N.ptr(g), N.ptr(z), B * cout, Ho, Wo, H, W, stride, st()), "ap_zero_insert2d")
+                        src, Hs, Ws = z, H, W
+                    else:
+                        src, Hs, Ws = g, Ho, Wo
+                    dx = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32)
+                    N.check(lib.ap_conv2d_fwd(N.ptr(src), N.ptr(self._conv_t(m)), None, None, N.ptr(dx), B, cout, Hs, Ws, Cin, kh, kw, 1,
+                                              kh - 1 - pad, 1, 0, cout, 0, st()), "ap_conv2d_fwd")
+                    acc(x, dx)
+                if res is not None:
+                    acc(res, g)
+            elif kind == "gn":
+                _, gn, x, ss, act, y = op
+                g = grads.pop(id(y), None)
+                if g is None:
+                    continue
+                _, C_, H, W = x.shape
+                dx = torch.empty_like(x)
+                dgm = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.weight] else None
+                dbt = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.bias] else None
+                dss = torch.empty_like(ss) if ss is not None else None
+                N.check(lib.ap_groupnorm_train_bwd(N.ptr(x), N.ptr(gn.weight.detach()), N.ptr(gn.bias.detach()), N.ptr(ss), N.ptr(g),
+                                                   N.ptr(dx), N.ptr(dgm), N.ptr(dbt), N.ptr(dss), gn_ws.data_ptr(), gn_ws.numel(), B, C_,
+                                                   H * W, gn.num_groups, float(gn.eps), act, st()), "ap_groupnorm_train_bwd")
+                if dgm is not None:
+                    pgrad[gn.weight] = dgm
+                if dbt is not None:
+                    pgrad[gn.bias] = dbt
+                if dss is not None:
+                    grads[id(ss)] = dss
+                acc(x, dx)
+            elif kind == "ss":                                    # this block's rows of the concatenated projection's cotangent
+                _, ss, off, n = op
+                g = grads.pop(id(ss), None)
+                if g is None:
+                    continue
+                if id(emb_proj) not in grads:
+                    grads[id(emb_proj)] = torch.zeros((B, total), device=dev, dtype=torch.float32)
+                N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(grads[id(emb_proj)]), B, n, 1, n, 0, total, off, st()), "ap_copy_channels")
+            elif kind == "drop":
+                _, h, y, draw = op
+                g = grads.pop(id(y), None)
+                if g is None:
+                    continue
+                tr = cfg
+                dh = torch.empty_like(g)
+                N.check(lib.ap_dropout(N.ptr(g), N.ptr(dh), B, h[0].numel(), tr["p"], tr["seed"], draw, tr["offset"], st()), "ap_dropout")
+                acc(h, dh)
+            elif kind == "embcat":
+                g = grads.pop(id(emb_proj), None)
+                if g is None:
+                    continue
+                ws_ = [rb.emb_layers[1].weight for rb in rbs]
+                bs_ = [rb.emb_layers[1].bias for rb in rbs]
+                dW, db = wgrad(g, emb_s, (total, ted) if any(want[w] for w in ws_) else None, any(want[b] for b in bs_),
+                               ted, 1, 1, total, 1, 1, 0, 1)
+                for rb, w, b in zip(rbs, ws_, bs_):               # split back onto each block's own Linear
+                    off, n = self._emb_rows[rb]
+                    if want[w]:
+                        pgrad[w] = dW[off:off + n].clone()
+                    if want[b]:
+                        pgrad[b] = db[off:off + n].clone()
+                d = torch.empty_like(emb_s)
+                N.check(lib.ap_conv2d_fwd(N.ptr(g), N.ptr(self._emb_cat_t()), None, None, N.ptr(d), B, total, 1, 1, ted, 1, 1, 1, 0, 1, 0,
+                                          total, 0, st()), "ap_conv2d_fwd")
+                acc(emb_s, d)
+            elif kind == "silu":
+                _, xin, y = op
+                g = grads.pop(id(y), None)
+                if g is None:
+                    continue
+                d = torch.empty_like(xin)
+                N.check(lib.ap_silu_bwd(N.ptr(xin), N.ptr(g), N.ptr(d), xin.numel(), st()), "ap_silu_bwd")
+                acc(xin, d)
+            elif kind == "attn":
+                _, qkv, att, heads = op
+                g = grads.pop(id(att), None)
+                if g is None:
+                    continue
+                _, C_, H, W = att.shape
+                dqkv = torch.empty_like(qkv)
+                stats = torch.empty(B * heads * H * W * 3, device=dev, dtype=torch.float32)
+                N.check(lib.ap_attention_qkv_bwd(N.ptr(qkv), N.ptr(att), N.ptr(g), N.ptr(dqkv), N.ptr(stats), B, C_, H * W, heads,
+                                                 st()), "ap_attention_qkv_bwd")
+                acc(qkv, dqkv)
+            elif kind == "up":
+                _, h, up = op
+                g = grads.pop(id(up), None)
+                if g is None:
+                    continue
+                _, C_, H, W = h.shape
+                dh = torch.empty_like(h)
+                N.check(lib.ap_upsample_nearest2x_bwd(N.ptr(g), N.ptr(dh), B * C_, H, W, st()), "ap_upsample_nearest2x_bwd")
+                acc(h, dh)
+            elif kind == "cat":
+                _, h, skip, cat = op
+                g = grads.pop(id(cat), None)
+                if g is None:
+                    continue
+                _, C1, H, W = h.shape
+                C2 = skip.shape[1]
+                dh, dsk = torch.empty_like(h), torch.empty_like(skip)
+                N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(dh), B, C1, H * W, C1 + C2, 0, C1, 0, st()), "ap_copy_channels")
+                N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(dsk), B, C2, H * W, C1 + C2, C1, C2, 0, st()), "ap_copy_channels")
+                acc(h, dh)
+                acc(skip, dsk)
+        return (grads.get(id(x_in)) if want_dx else None), pgrad
+
+
+class _UNetTrainFn(torch.autograd.Function):
+    """``UNetModel.forward_train``: the tape forward with dropout and the embedding path recorded; the backward is one reverse sweep
+    that leaves dx and every wanted parameter gradient (``UNetModel._train_grad``)."""
+
+    @staticmethod
+    def forward(ctx, x, model, timesteps, cfg, *params):
+        out, tape = model._forward_train(x, timesteps, cfg)
+        ctx.model, ctx.tape, ctx.params, ctx.cfg = model, tape, params, cfg
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if ctx.tape is None:
+            raise RuntimeError("audiopure_amd UNetModel.forward_train: the tape of this evaluation was freed by its first backward")
+        want = {p: bool(n) for p, n in zip(ctx.params, ctx.needs_input_grad[4:])}
+        with torch.no_grad(), torch.cuda.device(g.device):
+            dx, pgrad = ctx.model._train_grad(ctx.tape, g, want, ctx.needs_input_grad[0], ctx.cfg)
+        ctx.tape = None
+        return (dx, None, None, None) + tuple(pgrad.get(p) if want[p] else None for p in ctx.params)
 
 
 class _UNetInputGrad(torch.autograd.Function):

@@ -672,6 +672,35 @@ int ap_bn2d_train_bwd(const float *x, const float *y, const float *dy, const flo
                       float *dbeta, void *workspace, size_t ws_bytes, int B, int C, int HW, int x_cstride, int x_coff, int relu,
                       void *stream);
 
+/* ---- train-mode step of the Improved-Diffusion UNet (ap_unet_train.hip).  The reference trains it with
+ * improved_diffusion/train_util.py:191-229 (losses = diffusion.training_losses(ddp_model, micro, t); loss.backward()) at --dropout 0.3
+ * (spect_train_mpi_run.sh:1-8); its autograd forms what these entry points form.  Conv / Linear dW are ap_conv2d_wgrad, their biases
+ * ap_rowsum, the input-gradient sweep is ap_groupnorm_bwd's family.  Plain fp32; no floating-point atomics: every sum has a fixed
+ * order, sums over the batch run in fp64 and round once, two runs give equal bits.  A launch allocates nothing; every refusal is -22
+ * with ap_last_error set before any launch. ---- */
+/* GroupNorm32 + scale-shift + activation backward with every cotangent (the autograd of nn.py:17-19 normalization, unet.py:186-190
+ * `out_norm(h) * (1 + scale) + shift` and the SiLU behind it; unet.py:229 for the attention's norm, act 0).  Notation of
+ * ap_groupnorm_bwd: xh = (x - mean) rstd over the (sample, group) slab, y0 = gamma xh + beta, y1 = y0 (1 + sc) + sh, y = act(y1)
+ * (act 0 identity, 1 ReLU, 2 SiLU), e = dy act'(y1).  x, dy, dx [B][C][HW]; scale_shift and dss [B][2C] (scale first);
+ *   dss[b][c] = sum_hw e y0,  dss[b][C + c] = sum_hw e,
+ *   dbeta[c] = sum_b (1 + sc[b][c]) sum_hw e,  dgamma[c] = sum_b (1 + sc[b][c]) sum_hw e xh,  dx as ap_groupnorm_bwd forms it.
+ * Each of dx, dgamma, dbeta, dss may be NULL (not all); scale_shift == NULL: sc = sh = 0 and dss must be NULL.  gamma of either sign
+ * or 0 is served.  workspace: ap_groupnorm_train_workspace_bytes(B, C) bytes, 4-byte aligned, needed for dgamma / dbeta only. */
+size_t ap_groupnorm_train_workspace_bytes(int B, int C);
+int ap_groupnorm_train_bwd(const float *x, const float *gamma, const float *beta, const float *scale_shift, const float *dy, float *dx,
+                           float *dgamma, float *dbeta, float *dss, void *workspace, size_t ws_bytes, int B, int C, int HW, int groups,
+                           float eps, int act, void *stream);
+/* nn.Dropout(p) in training mode (unet.py:150-160, the ResBlock's out_layers) on a counter-based mask that is never stored: element e
+ * of sample b (n elements per sample) draws Philox4x32-10 with counter (e / 4, draw, low and high word of sample_offset + b), key =
+ * the two words of seed, and takes word e % 4: u = (r >> 8) 2^-24; kept iff u >= p (fp32), y = x s with s = fp32(1 / (1 - p)), else 0.
+ * The backward is the same call on dy; y may be x.  p = 0 copies bits; p outside [0, 1) is refused. */
+int ap_dropout(const float *x, float *y, int B, int n, float p, uint64_t seed, uint32_t draw, uint64_t sample_offset, void *stream);
+/* Backward of nn.py:12-14 SiLU (time_embed and emb_layers, unet.py:333-337,139-145): dx = dy s (1 + x (1 - s)), s = sigmoid(x). */
+int ap_silu_bwd(const float *x, const float *dy, float *dx, size_t n, void *stream);
+/* q_sample with one step per sample (gaussian_diffusion.py:188-206 with _extract_into_tensor's per-sample coefficients):
+ * out[b] = a[b] x0[b] + b[b] z[b]; x0, z, out [B][n], a and b device rows [B]. */
+int ap_qsample_rows(const float *x0, const float *z, const float *a, const float *b, float *out, int B, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
