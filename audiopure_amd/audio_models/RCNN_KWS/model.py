@@ -1,6 +1,8 @@
 """``KWSModel`` with the reference's constructor, state-dict keys and call surface
 (audio_models/RCNN_KWS/model.py:66-114; kws_adaptive_attack_eval.py:74-75 ``KWSModel(in_size=n_mels)`` +
-``load_state_dict``); the forward pass is one HIP kernel per batch (``ap_kws_fwd``).
+``load_state_dict``); the forward pass is one HIP kernel per batch (``ap_kws_fwd``).  In ``train()`` (the reference's
+audio_models/RCNN_KWS/train.py:84-121, 147-153, 177) the same kernel runs -- the model has no BatchNorm and no dropout -- and
+the backward is ``ap_kws_train_bwd``: the input gradient and every parameter gradient from one sweep.
 
 The submodules below exist only to own parameters under the reference's names (``CRNN_model.sepconv.{0,1}``,
 ``CRNN_model.gru`` incl. the ``_reverse`` tensors, ``attn_layer.{Wx_b,Vt}``, ``apply_attn.U``); their torch forward is
@@ -62,6 +64,40 @@ class _KwsInputGrad(torch.autograd.Function):
         return dx, None
 
 
+class _KwsTrainFn(torch.autograd.Function):
+    """log-probabilities with gradients with respect to every parameter and, where it asks for one, the mel input."""
+
+    @staticmethod
+    def forward(ctx, x, model, *params):
+        h = model._handle()
+        xc = x.detach().float().contiguous()
+        out = torch.empty((xc.shape[0], model.num_classes), device=xc.device, dtype=torch.float32)
+        N.check(N.lib().ap_kws_fwd(h, N.ptr(xc), N.ptr(out), xc.shape[0], xc.shape[2], N.stream()), "ap_kws_fwd")
+        ctx.model, ctx.x, ctx.shapes = model, xc, [(p.shape, p.dtype) for p in params]
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable       # a double backward raises
+    def backward(ctx, g):
+        model, xc = ctx.model, ctx.x
+        h = model._handle()
+        B, _, T = xc.shape
+        g = g.detach().float().contiguous()
+        dx = torch.empty_like(xc) if ctx.needs_input_grad[0] else None
+        n = N.lib().ap_kws_blob_elems(model.in_size, model.hidden_size, model.num_classes)
+        dparams = torch.empty(n, device=xc.device, dtype=torch.float32)
+        nws = N.lib().ap_kws_train_workspace_elems(h, B, T)
+        ws = torch.empty(nws, device=xc.device, dtype=torch.float32)
+        N.check(N.lib().ap_kws_train_bwd(h, N.ptr(xc), N.ptr(g), N.ptr(dx), N.ptr(dparams), N.ptr(ws), nws, B, T, N.stream()),
+                "ap_kws_train_bwd")
+        grads, at = [], 0
+        for need, (shape, dtype) in zip(ctx.needs_input_grad[2:], ctx.shapes):
+            grads.append(dparams[at:at + shape.numel()].view(shape).to(dtype) if need else None)
+            at += shape.numel()
+        assert at == n
+        return (dx, None, *grads)
+
+
 class KWSModel(nn.Module):
     _h = None                                  # class-level defaults: survive un-pickling without __init__
     _key = None
@@ -96,12 +132,19 @@ class KWSModel(nn.Module):
         dev = ts[0].device
         if dev.type != "cuda":
             raise N.NativeError("audiopure_amd KWSModel needs its parameters on a HIP device (.cuda()); no CPU path")
-        key = tuple((t.data_ptr(), t._version) for t in ts)
+        key = (dev,) + tuple((t.data_ptr(), t._version) for t in ts)
         if self._h is None or key != self._key:
+            blob = torch.cat([t.detach().reshape(-1).float() for t in ts]).contiguous()
+            if self._h is not None and self._key[0] == dev:
+                # an optimizer step moved versions (or a load moved pointers): refresh the handle's blob in stream order, with no
+                # allocation and no synchronise.  `blob` is a block of torch's caching allocator on this stream: whoever gets the
+                # block next runs on this stream too, after the copy
+                N.check(N.lib().ap_kws_set_weights(self._h, N.ptr(blob), blob.numel(), N.stream()), "ap_kws_set_weights")
+                self._key = key
+                return self._h
             if self._h is not None:
                 N.lib().ap_kws_destroy(self._h)
                 self._h = None
-            blob = torch.cat([t.detach().reshape(-1).float() for t in ts]).contiguous()
             h = C.c_void_p()
             N.check(N.lib().ap_kws_create(self.in_size, self.hidden_size, self.num_classes, N.ptr(blob), blob.numel(), N.stream(),
                                           C.byref(h)), "ap_kws_create")
@@ -111,14 +154,19 @@ class KWSModel(nn.Module):
     @N.on_device
     def forward(self, batch, hidden=None):
         """batch: mel-dB spectrogram [B,1,n_mels,T] (or [B,n_mels,T]) -> log-probabilities [B,num_classes]."""
-        if self.training:
-            raise NotImplementedError("audiopure_amd KWSModel: inference only; call .eval()")
+        if self.training and not all(p.is_cuda for p in self.parameters()):
+            raise NotImplementedError("audiopure_amd KWSModel: no CPU training path: off the device the module is inference only "
+                                      "(move it with .cuda(), or call .eval())")
         if hidden is not None:
             raise NotImplementedError("audiopure_amd KWSModel: a caller-supplied initial GRU state is not built "
                                       "(the scripts pass none, model.py:99-100)")
         x = batch.squeeze(1) if batch.ndim == 4 else batch
         if x.ndim != 3 or x.shape[1] != self.in_size:
             raise ValueError(f"expected [B,1,{self.in_size},T], got {tuple(batch.shape)}")
+        if self.training and torch.is_grad_enabled() and x.shape[0] > 0 and any(p.requires_grad for p in self.parameters()):
+            # the training step and the PGD inner loop in train() (train.py:84-121,147-153): parameter gradients, and the input's
+            # where it asks for one, from one backward (ap_kws_train_bwd)
+            return _KwsTrainFn.apply(x.float(), self, *self.parameters())
         if torch.is_grad_enabled() and x.requires_grad and x.shape[0] > 0:
             return _KwsInputGrad.apply(x.float(), self)          # white-box attack: d/d(mel) on the device (ap_kws_bwd)
         h = self._handle()

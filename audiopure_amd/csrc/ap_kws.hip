@@ -1,7 +1,9 @@
 // Keyword-spotting route: KWSModel.forward (audio_models/RCNN_KWS/model.py:66-114) and the
 // default-parameter torchaudio mel front-end its script builds (kws_adaptive_attack_eval.py:65-67), for clips of any
 // length.  Both are tiny next to the purifier (a 5-step GRU over 64 units for a 1 s clip): one workgroup per clip /
-// per frame, everything in LDS, plain fp32 VALU.
+// per frame, everything in LDS, plain fp32 VALU.  Further down: the input gradients of both (the white-box attack) and the
+// classifier's training step (audio_models/RCNN_KWS/train.py:147-153): the same sweep keeping its cotangents, then the parameter
+// gradients as contractions over (clip, step) on the exact-fp32 matrix instruction.
 #include "ap_common.h"
 
 #include <math.h>
@@ -306,11 +308,21 @@ __global__ void melspec_htk_bwd_gather_kernel(const float *__restrict__ scr, flo
 // ---- input gradients of the KWS route (white-box attack of kws_adaptive_attack_eval.py:132-143) ------------------
 // KWSModel: one workgroup per clip; the forward pass is recomputed keeping every GRU gate in a per-clip global scratch
 // (sequences are a handful of steps), then back-propagation through log-softmax / U / attention / the two GRU layers
-// (BPTT, both directions) / the separable conv.  Parameters are frozen: only d/d(mel) is formed.
+// (BPTT, both directions) / the separable conv.  kws_bwd_kernel<false> (ap_kws_bwd): parameters are frozen, only d/d(mel) is
+// formed.  kws_bwd_kernel<true> (ap_kws_train_bwd, phase 1) is the same sweep -- the same statements in the same order, so d/d(mel)
+// has the same bits -- that also keeps, per clip, what the parameter-gradient contractions of phase 2 read.  Every save is
+// [step t][unit] with the unit contiguous, so that a contraction over the items (clip, t) reads rows of consecutive floats:
+//   dg[l]   [2 dirs][T2][6H]  cotangents of the gate pre-activations: input side (r, z, n), then hidden side (r, z, n . r)
+//   th      [T2][2H]          tanh(Wx_b out_t + b)
+//   dpre    [T2][2H]          cotangent of Wx_b out_t + b
+//   dlogit  [64]              cotangent of the logits (K used)
+// and, from the sweep itself: seq[l] (a layer's input, [T2][2H]), gate[l] (h_prev at +4H of each [5H] row), e (holds de_t at the
+// end), cvec, dseq[0] (d pointwise output [T2][H] at the end), dw, ddw.
 struct KwsScr {                 // offsets (floats) into one clip's scratch
   size_t dw, seq[3], gate[2], e, a, cvec, dseq[2], din[2], ddw, total;
+  size_t dg[2], th, dpre, dlogit;                                  // training sweep only (beyond `total` of the plain sweep)
 };
-static __host__ __device__ KwsScr kws_scratch(int n_mels, int H, int T1, int T2) {
+static __host__ __device__ KwsScr kws_scratch(int n_mels, int H, int T1, int T2, bool train = false) {
   KwsScr o;
   size_t p = 0;
   o.dw = p; p += (size_t)n_mels * T1;
@@ -322,10 +334,15 @@ static __host__ __device__ KwsScr kws_scratch(int n_mels, int H, int T1, int T2)
   for (int i = 0; i < 2; i++) { o.dseq[i] = p; p += (size_t)T2 * 2 * H; }
   for (int i = 0; i < 2; i++) { o.din[i] = p; p += (size_t)T2 * 2 * H; }
   o.ddw = p; p += (size_t)n_mels * T1;
+  for (int l = 0; l < 2; l++) { o.dg[l] = p; if (train) p += (size_t)2 * T2 * 6 * H; }
+  o.th = p; if (train) p += (size_t)T2 * 2 * H;
+  o.dpre = p; if (train) p += (size_t)T2 * 2 * H;
+  o.dlogit = p; if (train) p += 64;
   o.total = p;
   return o;
 }
 
+template <bool TRAIN>
 __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ x, const float *__restrict__ dlogp,
                                                       float *__restrict__ dx, float *__restrict__ scratch,
                                                       const float *__restrict__ w, KwsOff o, KwsScr so, int n_mels, int H,
@@ -434,6 +451,8 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
     for (int k = 0; k < K; k++) s = __builtin_fmaf(w[o.u + (size_t)k * 2 * H + i], dlogit[k], s);
     tmp[i] = s;
   }
+  if (TRAIN)
+    for (int k = tid; k < K; k += nth) S[so.dlogit + k] = dlogit[k];
   __syncthreads();
   float *dout = S + so.dseq[1];                                    // gradient of the layer-1 output sequence
   if (tid == 0) {                                                  // da_t = dc . out_t ; softmax backward -> de
@@ -455,7 +474,18 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
       float q = w[o.wx_b + i];
       for (int k = 0; k < 2 * H; k++) q = __builtin_fmaf(wr[k], out[(size_t)t * 2 * H + k], q);
       const float th = tanhf(q);
-      dh[i] = e[t] * w[o.vt + i] * (1.0f - th * th);               // d pre-activation
+      if (!TRAIN) {
+        dh[i] = e[t] * w[o.vt + i] * (1.0f - th * th);             // d pre-activation
+      } else {
+        // The plain sweep's statement compiles to th * th and e_t Vt_i in one packed multiply, so its 1 - th^2 is NOT contracted
+        // into an fma; with the two saves below the compiler does contract it.  Spell the plain sweep's roundings out, so that
+        // d/d(mel) keeps ap_kws_bwd's bits (test_gpu_kws_train.py compares them).
+#pragma clang fp contract(off)
+        const float th2 = th * th, ev = e[t] * w[o.vt + i];
+        dh[i] = (1.0f - th2) * ev;
+        S[so.th + (size_t)t * 2 * H + i] = th;
+        S[so.dpre + (size_t)t * 2 * H + i] = dh[i];
+      }
     }
     __syncthreads();
     for (int k = tid; k < 2 * H; k += nth) {
@@ -491,6 +521,11 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
         gh[d * 3 * H + H + u] = dpre_z;
         gh[d * 3 * H + 2 * H + u] = dpre_n * r;
         tmp[i] = dht * z;                                          // direct path h_prev -> h
+        if (TRAIN) {
+          float *dg = S + so.dg[l] + ((size_t)d * T2 + t) * 6 * H;
+          dg[u] = dpre_r; dg[H + u] = dpre_z; dg[2 * H + u] = dpre_n;
+          dg[3 * H + u] = dpre_r; dg[4 * H + u] = dpre_z; dg[5 * H + u] = gh[d * 3 * H + 2 * H + u];
+        }
       }
       __syncthreads();
       for (int i = tid; i < 2 * H; i += nth) {                     // dh_prev = z dht + W_hh^T dgh
@@ -526,6 +561,7 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
       ddw[i] = s;
     }
     __syncthreads();
+    if (TRAIN && !dx) return;                                      // the caller wants no input gradient
     float *dxb = dx + (size_t)b * n_mels * T;
     for (int i = tid; i < n_mels * T; i += nth) {
       const int c = i / T, t = i - c * T;
@@ -537,6 +573,132 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
       dxb[i] = s;
     }
   }
+}
+
+// ---- parameter gradients of KWSModel (the reference trains it: audio_models/RCNN_KWS/train.py:147-153) ---------------------
+// Phase 2 of ap_kws_train_bwd: contractions of the sweep's saves over the items k = (clip b, step t), k = b T2 + t.  The item axis
+// is cut into KWS_SLICES contiguous slices -- a constant, not the device's CU count: the slicing sets the summation order -- each
+// slice writes a raw partial gradient blob, and kws_train_sum_kernel adds the slices in slice order in fp64, rounded once.  No
+// atomics: two runs give the same bits.
+constexpr int KWS_SLICES = 16;
+
+// G[m][n] = sum_k P[k][m] Q[k][n]: the row of item k starts at clip b's scratch + p + t pT (resp. q + t qT)
+struct KwsGemm { size_t p, q, dst; int pT, qT, M, N, tile0, tn; };
+struct KwsGemmTab { KwsGemm g[9]; int n, tiles; };
+
+// One wave per 64 x 64 tile of one matrix of the table and per slice, on the exact-fp32 matrix instruction (a k-ordered fmaf chain).
+// Both operands are contiguous along their free index, so the fragments (lane (j, hh): row/column j of item k + hh) are read
+// straight from global memory, 128 bytes per half-wave; nothing is staged.  grid (tab.tiles, KWS_SLICES)
+__global__ __launch_bounds__(64) void kws_train_gemm_kernel(const float *__restrict__ S, float *__restrict__ part, KwsGemmTab tab,
+                                                            size_t clip, size_t total, int T2, int items) {
+  const int tile = blockIdx.x, slice = blockIdx.y, lane = threadIdx.x, j = lane & 31, hh = lane >> 5;
+  KwsGemm g = tab.g[0];
+#pragma unroll
+  for (int i = 1; i < 9; i++)
+    if (i < tab.n && tile >= tab.g[i].tile0) g = tab.g[i];
+  const int lt = tile - g.tile0, m0 = (lt / g.tn) * 64, n0 = (lt % g.tn) * 64;
+  const int k0 = (int)((long long)slice * items / KWS_SLICES), k1 = (int)((long long)(slice + 1) * items / KWS_SLICES);
+  const bool mv0 = m0 + j < g.M, mv1 = m0 + 32 + j < g.M, nv0 = n0 + j < g.N, nv1 = n0 + 32 + j < g.N;
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) acc[i][c][r] = 0.f;
+  for (int k = k0; k < k1; k += 2) {
+    const int kk = k + hh;
+    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
+    if (kk < k1) {                                                 // an odd slice: the last step's second item is 0 . 0
+      const int b = kk / T2, t = kk - b * T2;
+      const float *pp = S + (size_t)b * clip + g.p + (size_t)t * g.pT + m0 + j;
+      const float *qp = S + (size_t)b * clip + g.q + (size_t)t * g.qT + n0 + j;
+      if (mv0) a0 = pp[0];
+      if (mv1) a1 = pp[32];
+      if (nv0) b0 = qp[0];
+      if (nv1) b1 = qp[32];
+    }
+    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+  }
+  float *out = part + (size_t)slice * total + g.dst;               // lane (j, hh): column n0 + 32 c + j, rows m0 + 32 i + rowoff(r, hh)
+#pragma unroll
+  for (int i = 0; i < 2; i++)
+#pragma unroll
+    for (int c = 0; c < 2; c++) {
+      const int n = n0 + 32 * c + j;
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int m = m0 + 32 * i + rowoff(r, hh);
+        if (m < g.M && n < g.N) out[(size_t)m * g.N + n] = acc[i][c][r];
+      }
+    }
+}
+
+// The small tensors, one thread per element and slice, a plain fmaf chain over the slice's items in item order:
+//   the eight GRU biases (sums of dg), Wx_b.bias (sum of dpre), Vt (de_t th_t), the pointwise conv (dpw[t][oc] dw[g cpg + c][8 t])
+//   and its bias, the depthwise conv (ddw[c][8 t] x[c][16 t + k]: ddw is 0 off the frames the pointwise conv reads) and its bias,
+//   and U (dlogit (x) cvec, over the clips).  grid (ceil(elements / 256), KWS_SLICES)
+__global__ __launch_bounds__(256) void kws_train_small_kernel(const float *__restrict__ x, const float *__restrict__ S,
+                                                              float *__restrict__ part, KwsOff o, KwsScr so, size_t total, int n_mels,
+                                                              int H, int K, int groups, int B, int T, int T1, int T2) {
+  const int slice = blockIdx.y;
+  int e = blockIdx.x * 256 + threadIdx.x;
+  const int items = B * T2;
+  const int k0 = (int)((long long)slice * items / KWS_SLICES), k1 = (int)((long long)(slice + 1) * items / KWS_SLICES);
+  const int cpg = n_mels / groups, opg = H / groups;
+  float *out = part + (size_t)slice * total;
+  // (p, pT): first factor at clip scratch + p + t pT; (q, qT): second factor, there or (kind 2) in x; kind 0: no second factor
+  size_t p = 0, q = 0, dst = 0;
+  int pT = 0, qT = 0, kind = -1;
+  if (e < 24 * H) {                                                // GRU biases
+    const int v = e / (3 * H), jn = e - v * 3 * H, l = v >> 2, d = (v >> 1) & 1, side = v & 1;
+    p = so.dg[l] + (size_t)d * T2 * 6 * H + side * 3 * H + jn; pT = 6 * H; kind = 0; dst = o.gru[l][d][2 + side] + jn;
+  } else if ((e -= 24 * H) < 2 * H) {
+    p = so.dpre + e; pT = 2 * H; kind = 0; dst = o.wx_b + e;
+  } else if ((e -= 2 * H) < 2 * H) {
+    p = so.e; pT = 1; q = so.th + e; qT = 2 * H; kind = 1; dst = o.vt + e;
+  } else if ((e -= 2 * H) < H * cpg) {
+    const int oc = e / cpg, c = e - oc * cpg, g = oc / opg;
+    p = so.dseq[0] + oc; pT = H; q = so.dw + (size_t)(g * cpg + c) * T1; qT = 8; kind = 1; dst = o.pw_w + e;
+  } else if ((e -= H * cpg) < H) {
+    p = so.dseq[0] + e; pT = H; kind = 0; dst = o.pw_b + e;
+  } else if ((e -= H) < n_mels * 5) {
+    const int c = e / 5, k = e - c * 5;
+    p = so.ddw + (size_t)c * T1; pT = 8; q = (size_t)c * T + k; qT = 16; kind = 2; dst = o.dw_w + e;
+  } else if ((e -= n_mels * 5) < n_mels) {
+    p = so.ddw + (size_t)e * T1; pT = 8; kind = 0; dst = o.dw_b + e;
+  } else if ((e -= n_mels) < K * 2 * H) {
+    kind = 3; dst = o.u + e;
+  }
+  if (kind < 0) return;
+  float s = 0.f;
+  if (kind == 3) {
+    const int kc = e / (2 * H), i = e - kc * 2 * H;
+    const int b0 = (int)((long long)slice * B / KWS_SLICES), b1 = (int)((long long)(slice + 1) * B / KWS_SLICES);
+    for (int b = b0; b < b1; b++) s = __builtin_fmaf(S[(size_t)b * so.total + so.dlogit + kc], S[(size_t)b * so.total + so.cvec + i], s);
+  } else {
+    int b = k0 / T2, t = k0 - b * T2;
+    for (int k = k0; k < k1; k++) {
+      const float *Sb = S + (size_t)b * so.total;
+      const float pv = Sb[p + (size_t)t * pT];
+      if (kind == 0) s += pv;
+      else s = __builtin_fmaf(pv, kind == 1 ? Sb[q + (size_t)t * qT] : x[(size_t)b * n_mels * T + q + (size_t)t * qT], s);
+      if (++t == T2) { t = 0; b++; }
+    }
+  }
+  out[dst] = s;
+}
+
+// dparams = slice 0 + slice 1 + ... in fp64, rounded once
+__global__ __launch_bounds__(256) void kws_train_sum_kernel(const float *__restrict__ part, float *__restrict__ out, size_t total) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  double s = 0.0;
+  for (int sl = 0; sl < KWS_SLICES; sl++) s += (double)part[(size_t)sl * total + e];
+  out[e] = (float)s;
 }
 
 }  // namespace ap
@@ -623,7 +785,7 @@ extern "C" int ap_kws_bwd(ap_kws *k, const float *mel, const float *dlogprobs, f
   const int T1 = (T - 5) / 2 + 1, T2 = T1 >= 1 ? (T1 - 1) / 8 + 1 : 0;
   if (T < 5 || T2 < 1) { set_error("ap_kws_bwd: %d mel frames are too few for the separable conv", T); return -22; }
   if (k->hidden > 128 || k->num_classes > 64) { set_error("ap_kws_bwd: hidden <= 128 and num_classes <= 64"); return -22; }
-  kws_bwd_kernel<<<B, 256, 0, (hipStream_t)stream>>>(mel, dlogprobs, dmel, scratch, k->blob,
+  kws_bwd_kernel<false><<<B, 256, 0, (hipStream_t)stream>>>(mel, dlogprobs, dmel, scratch, k->blob,
                                                      kws_layout(k->n_mels, k->hidden, k->num_classes),
                                                      kws_scratch(k->n_mels, k->hidden, T1, T2), k->n_mels, k->hidden,
                                                      k->num_classes, k->groups, T, T1, T2);
@@ -644,5 +806,63 @@ extern "C" int ap_melspec_db_htk_bwd(const float *x, const float *dout, float *d
   AP_HIP(hipGetLastError());
   melspec_htk_bwd_gather_kernel<<<dim3((L + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(scratch, dx, n_frames, L);
   AP_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---- training step (audio_models/RCNN_KWS/train.py:84-121 PGD inner loop, :147-153 the step, :177 validation in train()) ----
+extern "C" size_t ap_kws_train_workspace_elems(const ap_kws *k, int B, int T) {
+  if (!k || B < 1 || T < 5) return 0;
+  const int T1 = (T - 5) / 2 + 1, T2 = (T1 - 1) / 8 + 1;
+  return kws_scratch(k->n_mels, k->hidden, T1, T2, true).total * (size_t)B + (size_t)KWS_SLICES * k->n;
+}
+
+extern "C" int ap_kws_train_bwd(ap_kws *k, const float *mel, const float *dlogprobs, float *dmel, float *dparams, float *workspace,
+                                size_t workspace_elems, int B, int T, void *stream) {
+  if (!k || !mel || !dlogprobs || !dparams || !workspace) { set_error("ap_kws_train_bwd: null argument"); return -22; }
+  if (B < 1) { set_error("ap_kws_train_bwd: B = %d", B); return -22; }
+  if (T < 5) { set_error("ap_kws_train_bwd: %d mel frames are too few for the separable conv", T); return -22; }
+  if (k->hidden > 128 || k->num_classes > 64) { set_error("ap_kws_train_bwd: hidden <= 128 and num_classes <= 64"); return -22; }
+  const int T1 = (T - 5) / 2 + 1, T2 = (T1 - 1) / 8 + 1, H = k->hidden, K = k->num_classes;
+  if ((long long)B * T2 > 0x7fffffffLL) { set_error("ap_kws_train_bwd: B * T2 = %lld items", (long long)B * T2); return -22; }
+  const size_t need = ap_kws_train_workspace_elems(k, B, T);
+  if (workspace_elems < need) { set_error("ap_kws_train_bwd: workspace holds %zu floats, %zu needed", workspace_elems, need); return -22; }
+  const KwsOff o = kws_layout(k->n_mels, H, K);
+  const KwsScr so = kws_scratch(k->n_mels, H, T1, T2, true);
+  hipStream_t st = (hipStream_t)stream;
+  float *part = workspace + so.total * (size_t)B;
+  kws_bwd_kernel<true><<<B, 256, 0, st>>>(mel, dlogprobs, dmel, workspace, k->blob, o, so, k->n_mels, H, K, k->groups, T, T1, T2);
+  AP_HIP(hipGetLastError());
+  KwsGemmTab tab;
+  tab.n = 0; tab.tiles = 0;
+  auto add = [&](size_t p, int pT, int M, size_t q, int qT, int N, size_t dst) {
+    KwsGemm &g = tab.g[tab.n++];
+    g.p = p; g.pT = pT; g.M = M; g.q = q; g.qT = qT; g.N = N; g.dst = dst;
+    g.tile0 = tab.tiles; g.tn = (N + 63) / 64;
+    tab.tiles += ((M + 63) / 64) * g.tn;
+  };
+  for (int l = 0; l < 2; l++)
+    for (int d = 0; d < 2; d++) {
+      const size_t dg = so.dg[l] + (size_t)d * T2 * 6 * H;
+      add(dg, 6 * H, 3 * H, so.seq[l], 2 * H, l == 0 ? H : 2 * H, o.gru[l][d][0]);                       // weight_ih: dgi (x) layer input
+      add(dg + 3 * H, 6 * H, 3 * H, so.gate[l] + (size_t)d * T2 * 5 * H + 4 * H, 5 * H, H, o.gru[l][d][1]);   // weight_hh: dgh (x) h_prev
+    }
+  add(so.dpre, 2 * H, 2 * H, so.seq[2], 2 * H, 2 * H, o.wx_w);                                           // Wx_b.weight: dpre (x) out_t
+  kws_train_gemm_kernel<<<dim3(tab.tiles, KWS_SLICES), 64, 0, st>>>(workspace, part, tab, so.total, k->n, T2, B * T2);
+  AP_HIP(hipGetLastError());
+  const int cpg = k->n_mels / k->groups;
+  const int nsmall = 24 * H + 4 * H + H * cpg + H + 6 * k->n_mels + K * 2 * H;
+  kws_train_small_kernel<<<dim3((nsmall + 255) / 256, KWS_SLICES), 256, 0, st>>>(mel, workspace, part, o, so, k->n, k->n_mels, H, K,
+                                                                                  k->groups, B, T, T1, T2);
+  AP_HIP(hipGetLastError());
+  kws_train_sum_kernel<<<(unsigned)((k->n + 255) / 256), 256, 0, st>>>(part, dparams, k->n);
+  AP_HIP(hipGetLastError());
+  return 0;
+}
+
+// Refresh the handle's weights after an optimizer step: a stream-ordered copy into the existing blob, no allocation, no synchronise.
+extern "C" int ap_kws_set_weights(ap_kws *k, const float *blob_dev, size_t n_elems, void *stream) {
+  if (!k || !blob_dev) { set_error("ap_kws_set_weights: null argument"); return -22; }
+  if (n_elems != k->n) { set_error("ap_kws_set_weights: blob has %zu elements, expected %zu", n_elems, k->n); return -22; }
+  AP_HIP(hipMemcpyAsync(k->blob, blob_dev, n_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return 0;
 }

@@ -539,6 +539,19 @@ int ap_melspec_db_htk(const float *x, float *out, int n_mels, int B, int L, void
 size_t ap_kws_bwd_scratch_elems(const ap_kws *k, int B, int T);
 int ap_kws_bwd(ap_kws *k, const float *mel, const float *dlogprobs, float *dmel, float *scratch, int B, int T, void *stream);
 int ap_melspec_db_htk_bwd(const float *x, const float *dout, float *dx, float *scratch, int n_mels, int B, int L, void *stream);
+/* Training step of KWSModel (audio_models/RCNN_KWS/train.py:84-121 the PGD inner loop in train(), :147-153 CrossEntropyLoss +
+ * loss.backward() + Adam, :177 validation in train()).  The model has no BatchNorm and no dropout: the train-mode forward is
+ * ap_kws_fwd.  ap_kws_train_bwd: dlogprobs [B][K] -> dparams, one gradient blob in the layout of `blob_dev` (state-dict order),
+ * overwritten, and -- unless dmel is NULL -- dmel [B][n_mels][T] with the bits of ap_kws_bwd.  `workspace` holds
+ * ap_kws_train_workspace_elems floats: the per-clip saves of the sweep and 16 partial blobs that are summed in a fixed order
+ * (no atomics: two runs give the same bits).  Refused with -22 before any launch: a null handle or pointer (dmel excepted),
+ * B < 1, T < 5, a workspace too small, hidden > 128, num_classes > 64.
+ * ap_kws_set_weights: what the optimizer step (train.py:153) asks of the handle -- a stream-ordered copy of a new blob into the
+ * existing one, with no allocation and no synchronisation; n_elems is checked as by ap_kws_create. */
+size_t ap_kws_train_workspace_elems(const ap_kws *k, int B, int T);
+int ap_kws_train_bwd(ap_kws *k, const float *mel, const float *dlogprobs, float *dmel, float *dparams, float *workspace,
+                     size_t workspace_elems, int B, int T, void *stream);
+int ap_kws_set_weights(ap_kws *k, const float *blob_dev, size_t n_elems, void *stream);
 
 /* ---- input gradient of the eps-network (reference: the white-box attack back-propagates through
  * the defender, robustness_eval/white_box_attack.py:392,437-439; diffwave_sde.py:200-204 sdeint_adjoint).  The GEMM-shaped
