@@ -510,7 +510,10 @@ int ap_iir_bwd(const float *g, const float *ypre, const unsigned *minmax, float 
 size_t ap_psy_scratch_elems(int window, int hop, int B, int L);
 /* PsychoacousticMasker.calculate_threshold_and_psd_maximum (:61-86) for x [B][L] plus the stabilisation of
  * AudioAttack._stabilized_threshold_and_psd_maximum (:692-715): thr_stab [B][1025][F] = 10^(0.1 threshold),
- * psd_max_stab [B] = 10^(0.1 psd_max).  thr_db [B][1025][F] (the fp32 threshold in dB) and psd_max_db [B] may be NULL. */
+ * psd_max_stab [B] = 10^(0.1 psd_max).  thr_db [B][1025][F] (the fp32 threshold in dB) and psd_max_db [B] may be NULL.
+ * On return `scratch` holds the first stage: the fp32 PSD in dB, un-normalised and floored at -200, [B][F][1025], followed by
+ * its per-frame maxima [B][F] (B F 1026 floats in all; the rest of ap_psy_scratch_elems is not written).  The clip maximum
+ * psd_max is the maximum of a clip's F frame maxima; the threshold is computed from the PSD shifted by 96 - psd_max. */
 int ap_psy_threshold(const float *x, const double *tables, float *thr_stab, float *thr_db, float *psd_max_stab,
                      float *psd_max_db, float *scratch, int window, int hop, int B, int L, void *stream);
 /* AudioAttack._loss_gradient_masking_threshold (:610-690) for the perturbation delta [B][L]: loss [B] = mean over bins and

@@ -43,6 +43,98 @@ def test_restated_loss_and_grad_equal_the_reference_along_its_trajectory(G):
             assert np.abs(grad[b] - want[b]).max() <= 1e-5 * np.abs(want[b]).max()
 
 
+def _frames_of(name):
+    """(clip, hop, un-normalised PSD [F, 1025], normalised PSD [F, 1025]) of one edge clip."""
+    x, hop = R.edge_clips()[name]
+    p, _ = R.psd_db(x, hop)
+    p = np.ascontiguousarray(p.T)
+    return x, hop, p, R.normalised(p)[0]
+
+
+def _strict_maxima(row):
+    return np.nonzero((row[1:-1] > row[:-2]) & (row[1:-1] > row[2:]))[0] + 1
+
+
+def test_threshold_from_psd_is_the_kernel_layout_form_of_threshold():
+    x, hop = R.edge_clips()["hop700"]
+    m = P.PsychoacousticMasker(hop_size=hop)
+    p, mx = R.psd_db(x, hop)
+    thr, mx2 = R.threshold_from_psd(np.ascontiguousarray(p.T), m.bark, m.absolute_threshold_hearing)
+    assert thr.shape == (1025, 4) and thr.dtype == np.float32 and mx2.dtype == np.float32 and mx2 == mx
+    want, _ = R.threshold(x, hop)
+    assert np.array_equal(thr, want)
+    # the shift is the clip's, not the frame's: the loudest frame alone gives its column again, a quieter one does not
+    rows = p.T
+    loud = int(rows.max(axis=1).argmax())
+    assert np.array_equal(R.threshold_from_psd(rows[loud:loud + 1], m.bark, m.absolute_threshold_hearing)[0][:, 0], thr[:, loud])
+    other = (loud + 1) % 4
+    assert not np.array_equal(R.threshold_from_psd(rows[other:other + 1], m.bark, m.absolute_threshold_hearing)[0][:, 0],
+                              thr[:, other])
+
+
+def test_edge_clips_contain_what_the_gpu_tests_rely_on():
+    """tests/test_gpu_psy_edges.py runs these clips through the kernels; here the restatement shows that each one reaches the
+    branch it is named for, so that no GPU case can go vacuous."""
+    m = P.PsychoacousticMasker()
+    bark, ath = m.bark, m.absolute_threshold_hearing
+    clips = R.edge_clips()
+    assert {k: (len(x), hop) for k, (x, hop) in clips.items()} == {
+        "noise": (4908, 512), "one_frame": (2048, 512), "hop2048": (6161, 2048), "hop700": (4847, 700), "quiet": (4908, 512),
+        "constant": (4908, 512), "silent_middle": (4908, 512), "end_bins": (4908, 512), "impulses": (4908, 512)}
+    for k, (x, hop) in clips.items():               # seeded: the same clips in every process
+        assert np.array_equal(x, R.edge_clips()[k][0]) and x.dtype == np.float32
+    # the white-noise clips: every bin within 120 dB of the clip maximum, so the PSD comparison leaves nothing out
+    for name, F in (("noise", 6), ("one_frame", 1), ("hop2048", 3), ("hop700", 4), ("quiet", 6)):
+        _, _, p, _ = _frames_of(name)
+        assert p.shape == (F, 1025) and p.min() > p.max() - 120 and p.min() > -200
+    # sinusoids at bins 1 and 1023: both are strict maxima, pass the ATH filter and survive the bark-distance pass
+    _, _, _, pn = _frames_of("end_bins")
+    for f in range(3):
+        first, kept, _ = R.frame_maskers(pn[f], bark, ath)
+        assert first[0] == 1 and first[-1] == 1023 and kept[0] == 1 and kept[-1] == 1023 and len(kept) > 20
+    # a digitally silent frame inside a loud clip: -200 dB in every bin, a finite shift, no maskers, threshold = ATH
+    x, hop, p, pn = _frames_of("silent_middle")
+    assert not x[2560:2560 + 2048].any() and np.all(p[5] == -200) and np.isfinite(pn).all() and p.max() > -60
+    assert [len(R.frame_maskers(pn[f], bark, ath)[0]) > 0 for f in range(6)] == [True] * 5 + [False]
+    for f in range(2, 5):                           # the frames before it: windows that are partly silent
+        seg = x[f * hop:f * hop + 2048]
+        assert seg.any() and not seg.all()
+    thr, _ = R.threshold_from_psd(p, bark, ath)
+    assert np.array_equal(thr[:, 5], ath.astype(np.float32)) and np.isneginf(thr[:3, 5]).all() and np.isfinite(thr[3:]).all()
+    # a constant: all but the lowest bins at the floor, no strict maximum anywhere
+    _, _, p, pn = _frames_of("constant")
+    assert np.all(p[:, 2:] == -200) and np.all(p[:, :2] > -60)
+    assert all(len(_strict_maxima(pn[f])) == 0 for f in range(6))
+    # impulses: flat rows (plateaus where > and >= differ), frames 2 and 3 silent
+    x, _, p, pn = _frames_of("impulses")
+    assert np.all(p[2:4] == -200) and np.all(p[[0, 1, 4, 5]] > -200)
+    for f in (0, 1, 4, 5):
+        assert p[f].max() - p[f].min() < 1e-4 and (p[f][1:] == p[f][:-1]).sum() > 900
+        assert len(_strict_maxima(pn[f])) < (pn[f][1:-1] >= np.maximum(pn[f][:-2], pn[f][2:])).sum()
+    # loudness: the three clips of the batch peak 40 dB and more apart
+    mx = [float(R.psd_db(x, 512)[1]) for x in R.loudness_batch()]
+    assert mx[0] - mx[2] > 10 and mx[2] - mx[1] > 40
+    assert not R.loudness_batch()[2, 2560:2560 + 2048].any()
+
+
+@pytest.mark.parametrize("times_sd", (1, 2))
+@pytest.mark.parametrize("hop,L", R.LOSS_CASES)
+def test_loss_cases_activate_the_hinge_in_a_fifth_to_four_fifths_of_the_cells(hop, L, times_sd):
+    x, delta = R.loss_case(hop, L, times_sd)
+    assert x.shape == delta.shape == (2, L)
+    assert abs(delta.std() / x.std() - times_sd) < 0.05 * times_sd
+    thr, pm = zip(*[R.threshold(x[b], hop) for b in range(2)])
+    assert thr[0].shape == (1025, 1 + (L - 2048) // hop)
+    thr_stab, pm_stab = R.stabilised(np.stack(thr), np.array(pm))
+    assert abs(pm_stab[0] / pm_stab[1] - 1) > 1e-2                # two different normalisations in one batch
+    share = R.active_share(delta, thr_stab, pm_stab, hop)
+    assert share.shape == (2,) and np.all(share >= 0.2) and np.all(share <= 0.8), share
+    # the share is what the loss sees: the restated loss is the mean of the active excesses
+    loss, _ = R.loss_and_grad(delta, thr_stab, pm_stab, hop)
+    Pw = R.power(delta, pm_stab, hop)
+    assert np.allclose(loss, np.maximum(Pw - thr_stab, 0).mean(axis=(1, 2)), rtol=1e-12, atol=0)
+
+
 def test_host_tables_equal_the_reference_bit_for_bit(G):
     assert np.array_equal(P.hann_periodic(2048), G["window"])
     for sr in (16000, 44100):
