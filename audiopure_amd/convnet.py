@@ -453,6 +453,15 @@ class _TrainSweep:
         return self.grads[name], 0
 
 
+class _TrainRun:
+    """What the step loop needs to run a train plan: the module's live parameters and buffers by name and the per-plan device images
+    (``_train_images``); it leaves each ``bn`` step's [2][C] batch statistics and the counters of the layers that ran."""
+
+    def __init__(self, live, img):
+        self.live, self.img = live, img
+        self.stats, self.counters = {}, []
+
+
 def strict() -> bool:
     """``AUDIOPURE_STRICT=1``: the off-native routes of ``NativeConvNet.forward`` raise instead of running PyTorch operators."""
     import os
@@ -606,28 +615,56 @@ class NativeConvNet(nn.Module):
         if self._dev_weights is None or self._dev != dev:
             self._prepare(dev)
         N.use_conv_workspace(dev)
-        lib, W, B, st_ = N.lib(), self._dev_weights, x.shape[0], N.stream()
-        bufs = {self.plan.input.buf: x.detach().float().contiguous()}
+        return self._execute(x, self.plan)
+
+    def _execute(self, x, plan, tr=None):
+        """The one step loop of both plans -> (output, every buffer of the plan).  Two step kinds depend on the mode.  ``conv``: the
+        eval plan reads the image ``_prepare`` packed (BatchNorm folded in, ReLU and the precision flags in the launch); with ``tr``
+        (a ``_TrainRun``) the image is packed from the module's live weight before every launch and the launch carries no flag.
+        ``bn`` exists in train plans only: batch statistics into ``tr.stats``, the layer's counter into ``tr.counters``."""
+        lib, W, B, dev, st_ = N.lib(), self._dev_weights, x.shape[0], x.device, N.stream()
+        bufs = {plan.input.buf: x.detach().float().contiguous()}
 
         def buf(v):
             if v.buf not in bufs:
-                C_, H_, W_ = self.plan.buf_shape[v.buf]
+                C_, H_, W_ = plan.buf_shape[v.buf]
                 bufs[v.buf] = torch.empty((B, C_, H_, W_), device=dev, dtype=torch.float32)
             return bufs[v.buf]
 
-        for i, s in enumerate(self.plan.steps):
+        for i, s in enumerate(plan.steps):
             o, p = s.out, s.p
             ob = buf(o)
             if s.kind == "conv":
                 v = s.ins[0]
                 assert o.full
+                if tr is None:
+                    wimg, bias, flags = self._packed[i], (W[p["bk"]] if p["bk"] else None), int(p["relu"]) | self._conv_flags
+                else:
+                    assert not p["relu"]
+                    Cout, Cg, kh, kw = p["wshape"]
+                    wimg, bias, flags = tr.img["fwd"][i], (tr.live[p["bname"]].detach() if p["bname"] else None), 0
+                    N.check(lib.ap_conv2d_pack(N.ptr(tr.live[p["wname"]].detach()), None, N.ptr(wimg), Cout, Cg, kh, kw, p["groups"], st_),
+                            "ap_conv2d_pack")
                 res = N.ptr(buf(p["res"])) if p["res"] is not None else None
-                N.check(lib.ap_conv2d_fwd(N.ptr(buf(v)), N.ptr(self._packed[i]), N.ptr(W[p["bk"]]) if p["bk"] else None, res,
-                                          N.ptr(ob), B, v.C, v.H, v.W, o.C, p["kh"], p["kw"], p["stride"], p["pad"],
-                                          p["groups"], int(p["relu"]) | self._conv_flags, v.cstride, v.coff, st_), "ap_conv2d_fwd")
-            elif s.kind == "affine":
+                N.check(lib.ap_conv2d_fwd(N.ptr(buf(v)), N.ptr(wimg), N.ptr(bias), res, N.ptr(ob), B, v.C, v.H, v.W, o.C, p["kh"], p["kw"],
+                                          p["stride"], p["pad"], p["groups"], flags, v.cstride, v.coff, st_), "ap_conv2d_fwd")
+            elif s.kind == "bn":
                 v = s.ins[0]
                 assert o.full
+                live, ws = tr.live, tr.img["bn_ws"]
+                nbt = live.get(p["nbtname"])
+                mom = p["momentum"] if p["momentum"] is not None else 1.0 / (int(nbt) + 1)   # momentum=None: the cumulative average
+                stat = torch.empty((2, o.C), device=dev, dtype=torch.float32)
+                N.check(lib.ap_bn2d_train_fwd(N.ptr(buf(v)), N.ptr(live[p["wname"]].detach()), N.ptr(live[p["bname"]].detach()),
+                                              N.ptr(live[p["rmname"]]), N.ptr(live[p["rvname"]]), N.ptr(ob), N.ptr(stat), ws.data_ptr(),
+                                              ws.numel(), B, o.C, o.H * o.W, v.cstride, v.coff, p["eps"], mom, int(p["relu"]), st_),
+                        "ap_bn2d_train_fwd")
+                if nbt is not None:
+                    tr.counters.append(nbt)
+                tr.stats[i] = stat
+            elif s.kind == "affine":
+                v = s.ins[0]
+                assert o.full and (tr is None or p["sk"] is None)    # a train plan's affine steps are bare ReLUs (lower())
                 N.check(lib.ap_affine_nchw(N.ptr(buf(v)), N.ptr(W[p["sk"]]) if p["sk"] else None,
                                            N.ptr(W[p["hk"]]) if p["hk"] else None, N.ptr(ob), B, v.C, v.H * v.W, v.cstride,
                                            v.coff, int(p["relu"]), st_), "ap_affine_nchw")
@@ -644,7 +681,7 @@ class NativeConvNet(nn.Module):
                 v = s.ins[0]
                 N.check(lib.ap_pool2d(N.ptr(buf(v)), N.ptr(ob), B * v.C, v.H, v.W, p["k"], p["stride"], p["pad"],
                                       int(p["is_max"]), st_), "ap_pool2d")
-        o = self.plan.output
+        o = plan.output
         out = buf(o)
         assert o.full
         return (out.view(B, -1) if (o.H == 1 and o.W == 1) else out), bufs
@@ -710,67 +747,11 @@ class NativeConvNet(nn.Module):
             raise ValueError(f"expected [B, {self._train_chw}], got {tuple(x.shape)}")
         dev = x.device
         N.use_conv_workspace(dev)
-        lib, st_, B = N.lib(), N.stream(), x.shape[0]
-        live, img = self._live_tensors(), self._train_images(tplan, dev)
-        bufs = {tplan.input.buf: x.detach().float().contiguous()}
-        stats, counters = {}, []
-        ws, ws_bytes = img["bn_ws"].data_ptr(), img["bn_ws"].numel()
-
-        def buf(v):
-            if v.buf not in bufs:
-                C_, H_, W_ = tplan.buf_shape[v.buf]
-                bufs[v.buf] = torch.empty((B, C_, H_, W_), device=dev, dtype=torch.float32)
-            return bufs[v.buf]
-
-        for i, s in enumerate(tplan.steps):
-            o, p = s.out, s.p
-            ob = buf(o)
-            if s.kind == "conv":
-                v = s.ins[0]
-                assert o.full and not p["relu"]
-                Cout, Cg, kh, kw = p["wshape"]
-                N.check(lib.ap_conv2d_pack(N.ptr(live[p["wname"]].detach()), None, N.ptr(img["fwd"][i]), Cout, Cg, kh, kw, p["groups"], st_),
-                        "ap_conv2d_pack")
-                res = N.ptr(buf(p["res"])) if p["res"] is not None else None
-                N.check(lib.ap_conv2d_fwd(N.ptr(buf(v)), N.ptr(img["fwd"][i]), N.ptr(live[p["bname"]].detach()) if p["bname"] else None, res,
-                                          N.ptr(ob), B, v.C, v.H, v.W, o.C, kh, kw, p["stride"], p["pad"], p["groups"], 0, v.cstride,
-                                          v.coff, st_), "ap_conv2d_fwd")
-            elif s.kind == "bn":
-                v = s.ins[0]
-                assert o.full
-                nbt = live.get(p["nbtname"])
-                mom = p["momentum"] if p["momentum"] is not None else 1.0 / (int(nbt) + 1)   # momentum=None: the cumulative average
-                stat = torch.empty((2, o.C), device=dev, dtype=torch.float32)
-                N.check(lib.ap_bn2d_train_fwd(N.ptr(buf(v)), N.ptr(live[p["wname"]].detach()), N.ptr(live[p["bname"]].detach()),
-                                              N.ptr(live[p["rmname"]]), N.ptr(live[p["rvname"]]), N.ptr(ob), N.ptr(stat), ws, ws_bytes,
-                                              B, o.C, o.H * o.W, v.cstride, v.coff, p["eps"], mom, int(p["relu"]), st_), "ap_bn2d_train_fwd")
-                if nbt is not None:
-                    counters.append(nbt)
-                stats[i] = stat
-            elif s.kind == "affine":
-                v = s.ins[0]
-                assert o.full and p["sk"] is None
-                N.check(lib.ap_affine_nchw(N.ptr(buf(v)), None, None, N.ptr(ob), B, v.C, v.H * v.W, v.cstride, v.coff, int(p["relu"]), st_),
-                        "ap_affine_nchw")
-            elif s.kind == "add":
-                a, b = s.ins
-                assert o.full
-                N.check(lib.ap_add_nchw(N.ptr(buf(a)), N.ptr(buf(b)), N.ptr(ob), B, a.C, a.H * a.W, a.cstride, a.coff,
-                                        b.cstride, b.coff, int(p["relu"]), st_), "ap_add_nchw")
-            elif s.kind == "copy":
-                v = s.ins[0]
-                N.check(lib.ap_copy_channels(N.ptr(buf(v)), N.ptr(ob), B, v.C, v.H * v.W, v.cstride, v.coff, o.cstride,
-                                             o.coff, st_), "ap_copy_channels")
-            elif s.kind == "pool":
-                v = s.ins[0]
-                N.check(lib.ap_pool2d(N.ptr(buf(v)), N.ptr(ob), B * v.C, v.H, v.W, p["k"], p["stride"], p["pad"],
-                                      int(p["is_max"]), st_), "ap_pool2d")
-        if counters:                                             # num_batches_tracked += 1, every BatchNorm's int64 counter in one
-            torch._foreach_add_(counters, 1)                     # fused torch call: the step's only torch operator
-        o = tplan.output
-        out = buf(o)
-        assert o.full
-        return (out.view(B, -1) if (o.H == 1 and o.W == 1) else out), ((bufs, stats) if keep else None)
+        tr = _TrainRun(self._live_tensors(), self._train_images(tplan, dev))
+        out, bufs = self._execute(x, tplan, tr)
+        if tr.counters:                                          # num_batches_tracked += 1, every BatchNorm's int64 counter in one
+            torch._foreach_add_(tr.counters, 1)                  # fused torch call: the step's only torch operator
+        return out, ((bufs, tr.stats) if keep else None)
 
     # ---- input gradient (SURVEY section 8 f-1 for the spectrogram classifiers) ------------------------------------
     def _prepare_backward(self):

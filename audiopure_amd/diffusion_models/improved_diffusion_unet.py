@@ -20,6 +20,13 @@ import torch.nn as nn
 from .. import _native as N
 
 
+def _pack(w, cout, cin, kh, kw):
+    """The ap_conv2d_fwd image of the contiguous weight ``w`` (viewed as [cout, cin, kh, kw], one group), on the current stream."""
+    img = torch.empty(N.lib().ap_conv2d_packed_elems(cout, cin, kh, kw, 1), device=w.device, dtype=torch.float32)
+    N.check(N.lib().ap_conv2d_pack(N.ptr(w), None, N.ptr(img), cout, cin, kh, kw, 1, N.stream()), "ap_conv2d_pack")
+    return img
+
+
 # ---- parameter holders with the reference's attribute tree -----------------------------------------------------
 class ResBlock(nn.Module):
     def __init__(self, channels, emb_channels, out_channels):
@@ -125,16 +132,14 @@ class UNetModel(nn.Module):
         key = (dev, tuple((p._version, p.data_ptr()) for p in ps))
         if key == self._key:
             return
-        lib, packed = N.lib(), {}
+        packed = {}
         for m in self.modules():
             if isinstance(m, (nn.Conv2d, nn.Conv1d, nn.Linear)):
                 w = m.weight.detach().float().contiguous()
                 cout = w.shape[0]
                 cin_g = w.shape[1]
                 kh, kw = (w.shape[2], w.shape[3]) if w.dim() == 4 else (1, 1)
-                wT = torch.empty(lib.ap_conv2d_packed_elems(cout, cin_g, kh, kw, 1), device=dev, dtype=torch.float32)
-                N.check(lib.ap_conv2d_pack(N.ptr(w), None, N.ptr(wT), cout, cin_g, kh, kw, 1, N.stream()), "ap_conv2d_pack")
-                packed[m] = (wT, m.bias.detach().float().contiguous() if m.bias is not None else None, cout, kh, kw,
+                packed[m] = (_pack(w, cout, cin_g, kh, kw), m.bias.detach().float().contiguous() if m.bias is not None else None, cout, kh, kw,
                              (m.stride[0] if hasattr(m, "stride") else 1), (m.padding[0] if hasattr(m, "padding") else 0))
         # every ResBlock projects the SAME embedding vector (unet.py:182, emb_layers = SiLU -> Linear): one GEMM over the
         # concatenated rows of all those Linear layers replaces one 256-column launch per block (24 of them per evaluation,
@@ -142,9 +147,7 @@ class UNetModel(nn.Module):
         rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
         wcat = torch.cat([rb.emb_layers[1].weight.detach().float() for rb in rbs], 0).contiguous()
         bcat = torch.cat([rb.emb_layers[1].bias.detach().float() for rb in rbs], 0).contiguous()
-        wT = torch.empty(lib.ap_conv2d_packed_elems(wcat.shape[0], wcat.shape[1], 1, 1, 1), device=dev, dtype=torch.float32)
-        N.check(lib.ap_conv2d_pack(N.ptr(wcat), None, N.ptr(wT), wcat.shape[0], wcat.shape[1], 1, 1, 1, N.stream()), "ap_conv2d_pack")
-        self._emb_cat = (wT, bcat, wcat.shape[0])
+        self._emb_cat = (_pack(wcat, wcat.shape[0], wcat.shape[1], 1, 1), bcat, wcat.shape[0])
         self._emb_rows, off = {}, 0
         for rb in rbs:
             n = rb.emb_layers[1].weight.shape[0]
@@ -244,18 +247,14 @@ class UNetModel(nn.Module):
                 h = self._resblock(layer, h, emb_proj, dest=d)
             elif isinstance(layer, AttentionBlock):
                 h = self._attention(layer, h, dest=d)
-            elif isinstance(layer, Upsample) and d is not None:
-                up = torch.empty((B, C_, 2 * H, 2 * W), device=h.device, dtype=torch.float32)
-                N.check(N.lib().ap_upsample_nearest2x(N.ptr(h), N.ptr(up), B * C_, H, W, N.stream()), "ap_upsample_nearest2x")
-                h = self._conv(layer.conv, up, B, C_, 2 * H, 2 * W, dest=d)
             elif isinstance(layer, Downsample):
                 h = self._conv(layer.op, h, B, C_, H, W)
             elif isinstance(layer, Upsample):
                 up = torch.empty((B, C_, 2 * H, 2 * W), device=h.device, dtype=torch.float32)
                 N.check(N.lib().ap_upsample_nearest2x(N.ptr(h), N.ptr(up), B * C_, H, W, N.stream()), "ap_upsample_nearest2x")
-                if self._tape is not None:
-                    self._tape.append(("up", h, up))
-                h = self._conv(layer.conv, up, B, C_, 2 * H, 2 * W)
+                if self._tape is not None:                      # (then d is None: _forward hands out a concatenation buffer
+                    self._tape.append(("up", h, up))            #  only when it records no tape -- `direct`)
+                h = self._conv(layer.conv, up, B, C_, 2 * H, 2 * W, dest=d)
             elif isinstance(layer, nn.Conv2d):
                 h = self._conv(layer, h, B, C_, H, W)
             else:
@@ -347,7 +346,7 @@ class UNetModel(nn.Module):
         Bc, C_, H, W = h.shape
         return self._conv(self.out[2], self._gn(self.out[0], h), Bc, C_, H, W)                     # :494
 
-    # ---- input gradient: reverse sweep over the tape of one evaluation -----------------------------------------------
+    # ---- input gradient: the reverse sweep (_sweep, below) over the tape of one evaluation ----------------------------
     def _conv_t(self, m):
         """Packed image of the transposed convolution of ``m`` (spatially flipped, in/out swapped)."""
         if m not in self._packed_t:
@@ -357,93 +356,13 @@ class UNetModel(nn.Module):
             if w.dim() == 3:
                 w = w[..., None]
             wt = w.flip(2, 3).permute(1, 0, 2, 3).contiguous()
-            co, ci, kh, kw = wt.shape
-            img = torch.empty(N.lib().ap_conv2d_packed_elems(co, ci, kh, kw, 1), device=wt.device, dtype=torch.float32)
-            N.check(N.lib().ap_conv2d_pack(N.ptr(wt), None, N.ptr(img), co, ci, kh, kw, 1, N.stream()), "ap_conv2d_pack")
-            self._packed_t[m] = img
+            self._packed_t[m] = _pack(wt, *wt.shape)
         return self._packed_t[m]
 
     @N.on_device
     def input_grad(self, tape, dout):
         """J^T dout of the evaluation ``tape`` came from (parameters and the timestep embedding are constants)."""
-        lib, st = N.lib(), N.stream
-        flags = getattr(self, "_conv_flags", 0)
-        out_t = tape[-1][4]
-        grads = {id(out_t): dout.detach().float().contiguous()}
-
-        def acc(t, g):
-            k = id(t)
-            if k in grads:
-                N.check(lib.ap_axpbyc(N.ptr(grads[k]), N.ptr(g), N.ptr(grads[k]), 1.0, 1.0, 0.0, g.numel(), st()), "ap_axpbyc")
-            else:
-                grads[k] = g
-
-        for op in reversed(tape):
-            kind = op[0]
-            if kind == "conv":
-                _, m, x, res, out, (B, Cin, H, W) = op
-                g = grads.pop(id(out), None)
-                if g is None:
-                    continue
-                _, _, cout, kh, kw, stride, pad = self._packed[m]
-                Ho, Wo = out.shape[2], out.shape[3]
-                if stride != 1:                                   # Downsample: spread dy onto the input grid first
-                    z = torch.empty((B, cout, H, W), device=g.device, dtype=torch.float32)
-                    N.check(lib.ap_zero_insert2d(N.ptr(g), N.ptr(z), B * cout, Ho, Wo, H, W, stride, st()), "ap_zero_insert2d")
-                    src, Hs, Ws = z, H, W
-                else:
-                    src, Hs, Ws = g, Ho, Wo
-                dx = torch.empty((B, Cin, H, W), device=g.device, dtype=torch.float32)
-                N.check(lib.ap_conv2d_fwd(N.ptr(src), N.ptr(self._conv_t(m)), None, None, N.ptr(dx), B, cout, Hs, Ws, Cin, kh, kw, 1,
-                                          kh - 1 - pad, 1, flags, cout, 0, st()), "ap_conv2d_fwd")
-                acc(x, dx)
-                if res is not None:
-                    acc(res, g)
-            elif kind == "gn":
-                _, gn, x, ss, act, y = op
-                g = grads.pop(id(y), None)
-                if g is None:
-                    continue
-                B, C_, H, W = x.shape
-                dx = torch.empty_like(x)
-                N.check(lib.ap_groupnorm_bwd(N.ptr(x), N.ptr(gn.weight.detach()), N.ptr(gn.bias.detach()), N.ptr(ss), N.ptr(g),
-                                             N.ptr(dx), B, C_, H * W, gn.num_groups, float(gn.eps), act, st()), "ap_groupnorm_bwd")
-                acc(x, dx)
-            elif kind == "attn":
-                _, qkv, att, heads = op
-                g = grads.pop(id(att), None)
-                if g is None:
-                    continue
-                B, C_, H, W = att.shape
-                dqkv = torch.empty_like(qkv)
-                stats = torch.empty(B * heads * H * W * 3, device=g.device, dtype=torch.float32)
-                N.check(lib.ap_attention_qkv_bwd(N.ptr(qkv), N.ptr(att), N.ptr(g), N.ptr(dqkv), N.ptr(stats), B, C_, H * W, heads,
-                                                 st()), "ap_attention_qkv_bwd")
-                acc(qkv, dqkv)
-            elif kind == "up":
-                _, h, up = op
-                g = grads.pop(id(up), None)
-                if g is None:
-                    continue
-                B, C_, H, W = h.shape
-                dh = torch.empty_like(h)
-                N.check(lib.ap_upsample_nearest2x_bwd(N.ptr(g), N.ptr(dh), B * C_, H, W, st()), "ap_upsample_nearest2x_bwd")
-                acc(h, dh)
-            elif kind == "cat":
-                _, h, skip, cat = op
-                g = grads.pop(id(cat), None)
-                if g is None:
-                    continue
-                B, C1, H, W = h.shape
-                C2 = skip.shape[1]
-                dh, dsk = torch.empty_like(h), torch.empty_like(skip)
-                N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(dh), B, C1, H * W, C1 + C2, 0, C1, 0, st()), "ap_copy_channels")
-                N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(dsk), B, C2, H * W, C1 + C2, C1, C2, 0, st()), "ap_copy_channels")
-                acc(h, dh)
-                acc(skip, dsk)
-            elif kind == "in":
-                return grads[id(op[1])]
-        raise RuntimeError("tape without an input record")
+        return self._sweep(tape, dout)
 
     # ---- training step: eps on an autograd node over (x, every parameter) --------------------------------------------
     def _dropout_config(self, dropout):
@@ -484,31 +403,19 @@ class UNetModel(nn.Module):
         if "embcat" not in self._packed_t:
             rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
             wt = torch.cat([rb.emb_layers[1].weight.detach().float() for rb in rbs], 0).t().contiguous()[..., None, None]
-            co, ci = wt.shape[0], wt.shape[1]
-            img = torch.empty(N.lib().ap_conv2d_packed_elems(co, ci, 1, 1, 1), device=wt.device, dtype=torch.float32)
-            N.check(N.lib().ap_conv2d_pack(N.ptr(wt.contiguous()), None, N.ptr(img), co, ci, 1, 1, 1, N.stream()), "ap_conv2d_pack")
-            self._packed_t["embcat"] = img
+            self._packed_t["embcat"] = _pack(wt, *wt.shape)
         return self._packed_t["embcat"]
 
     def _train_grad(self, tape, dout, want, want_dx, cfg):
-        """The reverse sweep of ``input_grad`` with every parameter cotangent: per conv op dW (ap_conv2d_wgrad) and db (ap_rowsum) from
+        """The reverse sweep with every parameter cotangent: per conv op dW (ap_conv2d_wgrad) and db (ap_rowsum) from
         the live weights' taped activations, per gn op ap_groupnorm_train_bwd, per dropout op ap_dropout on the cotangent, the FiLM
         cotangents gathered into one [B][total] row block for the concatenated emb_layers GEMM, then the time_embed path.
         ``want``: {parameter: bool}.  -> (dx or None, {parameter: gradient})."""
-        lib, st = N.lib(), N.stream
+        lib = N.lib()
         self._prepare()                                           # the transposed images belong to the weights the forward read
-        dev = dout.device
-        out_t = tape[-1][4]
-        B = out_t.shape[0]
-        grads = {id(out_t): dout.detach().float().contiguous()}
-        pgrad = {}
-        x_in = next(op[1] for op in tape if op[0] == "in")
-        no_dx = {id(op[1]) for op in tape if op[0] == "notgrad"}
-        if not want_dx:
-            no_dx.add(id(x_in))
+        dev, B = dout.device, tape[-1][4].shape[0]
         emb_s, emb_proj = next((op[1], op[2]) for op in tape if op[0] == "embcat")
         total, ted = emb_proj.shape[1], emb_s.shape[1]
-        rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
 
         # one workspace per kind, sized to the largest op of this tape (torch's allocator; the launches allocate nothing)
         wg = [lib.ap_conv2d_wgrad_workspace_bytes(B, ted, 1, 1, total, 1, 1, 1, 0, 1)]
@@ -524,8 +431,33 @@ class UNetModel(nn.Module):
                 wg.append(nb)
             elif op[0] == "gn":
                 gnb.append(lib.ap_groupnorm_train_workspace_bytes(B, op[2].shape[1]))
-        wg_ws = torch.empty(max(wg), device=dev, dtype=torch.uint8)
-        gn_ws = torch.empty(max(max(gnb), 4), device=dev, dtype=torch.uint8)
+        tr = _TrainSweep(want, want_dx, cfg, emb_s, emb_proj, wg_ws=torch.empty(max(wg), device=dev, dtype=torch.uint8),
+                         gn_ws=torch.empty(max(max(gnb), 4), device=dev, dtype=torch.uint8))
+        return self._sweep(tape, dout, tr), tr.pgrad
+
+    # ---- the reverse sweep, of input_grad and of _train_grad ---------------------------------------------------------
+    def _sweep(self, tape, dout, tr=None):
+        """The one reverse sweep over the tape of an evaluation.  Without ``tr`` it is the input gradient: it ends at the ``in`` record
+        and returns J^T dout.  With ``tr`` (a ``_TrainSweep``) it runs the whole tape of a ``forward_train``, leaves the wanted parameter
+        cotangents in ``tr.pgrad`` and returns dx or None.  Two launches differ by mode: the transposed convolution carries the
+        precision flags only for the input gradient (``forward_train`` is fp32), and a ``gn`` record goes through ap_groupnorm_bwd
+        or ap_groupnorm_train_bwd -- different reduction trees, so their dx differ in the last bits and each mode keeps its own.
+        The ``ss``, ``drop``, ``embcat`` and ``silu`` records exist on a ``forward_train`` tape only."""
+        lib, st = N.lib(), N.stream
+        dev = dout.device
+        flags = getattr(self, "_conv_flags", 0) if tr is None else 0
+        out_t = tape[-1][4]
+        B = out_t.shape[0]
+        grads = {id(out_t): dout.detach().float().contiguous()}
+        no_dx = set()                                             # inputs of conv records that get no gradient
+        if tr is not None:
+            want, pgrad, emb_s, emb_proj = tr.want, tr.pgrad, tr.emb_s, tr.emb_proj
+            total, ted = emb_proj.shape[1], emb_s.shape[1]
+            rbs = [m for m in self.modules() if isinstance(m, ResBlock)]
+            x_in = next(op[1] for op in tape if op[0] == "in")
+            no_dx = {id(op[1]) for op in tape if op[0] == "notgrad"}
+            if not tr.want_dx:
+                no_dx.add(id(x_in))
 
         def acc(t, g):
             k = id(t)
@@ -537,8 +469,8 @@ class UNetModel(nn.Module):
         def wgrad(dy, xa, w, bias, Cin, H, W, cout, k, stride, pad, L):
             if w is not None:
                 dW = torch.empty(w, device=dev, dtype=torch.float32)
-                N.check(lib.ap_conv2d_wgrad(N.ptr(dy), N.ptr(xa), N.ptr(dW), wg_ws.data_ptr(), wg_ws.numel(), B, Cin, H, W, cout, k, k,
-                                            stride, pad, 1, Cin, 0, 0, st()), "ap_conv2d_wgrad")
+                N.check(lib.ap_conv2d_wgrad(N.ptr(dy), N.ptr(xa), N.ptr(dW), tr.wg_ws.data_ptr(), tr.wg_ws.numel(), B, Cin, H, W, cout, k,
+                                            k, stride, pad, 1, Cin, 0, 0, st()), "ap_conv2d_wgrad")
             else:
                 dW = None
             if bias:
@@ -550,19 +482,24 @@ class UNetModel(nn.Module):
 
         for op in reversed(tape):
             kind = op[0]
+            if kind == "in":
+                if tr is None:
+                    return grads[id(op[1])]
+                continue
+            g = grads.pop(id(op[_OUT[kind]]), None) if kind in _OUT else None
+            if g is None:                                         # nothing downstream used this value (or a "notgrad" mark)
+                continue
             if kind == "conv":
                 _, m, x, res, out, (_, Cin, H, W) = op
-                g = grads.pop(id(out), None)
-                if g is None:
-                    continue
                 _, _, cout, kh, kw, stride, pad = self._packed[m]
                 Ho, Wo = out.shape[2], out.shape[3]
-                dW, db = wgrad(g, x, tuple(m.weight.shape) if want[m.weight] else None, m.bias is not None and want[m.bias],
-                               Cin, H, W, cout, kh, stride, pad, Ho * Wo)
-                if dW is not None:
-                    pgrad[m.weight] = dW
-                if db is not None:
-                    pgrad[m.bias] = db
+                if tr is not None:
+                    dW, db = wgrad(g, x, tuple(m.weight.shape) if want[m.weight] else None, m.bias is not None and want[m.bias],
+                                   Cin, H, W, cout, kh, stride, pad, Ho * Wo)
+                    if dW is not None:
+                        pgrad[m.weight] = dW
+                    if db is not None:
+                        pgrad[m.bias] = db
                 if id(x) not in no_dx:
                     if stride != 1:                               # Downsample: spread dy onto the input grid first
                         z = torch.empty((B, cout, H, W), device=dev, dtype=torch.float32)
@@ -572,51 +509,44 @@ class UNetModel(nn.Module):
                         src, Hs, Ws = g, Ho, Wo
                     dx = torch.empty((B, Cin, H, W), device=dev, dtype=torch.float32)
                     N.check(lib.ap_conv2d_fwd(N.ptr(src), N.ptr(self._conv_t(m)), None, None, N.ptr(dx), B, cout, Hs, Ws, Cin, kh, kw, 1,
-                                              kh - 1 - pad, 1, 0, cout, 0, st()), "ap_conv2d_fwd")
+                                              kh - 1 - pad, 1, flags, cout, 0, st()), "ap_conv2d_fwd")
                     acc(x, dx)
                 if res is not None:
                     acc(res, g)
             elif kind == "gn":
                 _, gn, x, ss, act, y = op
-                g = grads.pop(id(y), None)
-                if g is None:
-                    continue
                 _, C_, H, W = x.shape
                 dx = torch.empty_like(x)
-                dgm = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.weight] else None
-                dbt = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.bias] else None
-                dss = torch.empty_like(ss) if ss is not None else None
-                N.check(lib.ap_groupnorm_train_bwd(N.ptr(x), N.ptr(gn.weight.detach()), N.ptr(gn.bias.detach()), N.ptr(ss), N.ptr(g),
-                                                   N.ptr(dx), N.ptr(dgm), N.ptr(dbt), N.ptr(dss), gn_ws.data_ptr(), gn_ws.numel(), B, C_,
-                                                   H * W, gn.num_groups, float(gn.eps), act, st()), "ap_groupnorm_train_bwd")
-                if dgm is not None:
-                    pgrad[gn.weight] = dgm
-                if dbt is not None:
-                    pgrad[gn.bias] = dbt
-                if dss is not None:
-                    grads[id(ss)] = dss
+                if tr is None:
+                    N.check(lib.ap_groupnorm_bwd(N.ptr(x), N.ptr(gn.weight.detach()), N.ptr(gn.bias.detach()), N.ptr(ss), N.ptr(g),
+                                                 N.ptr(dx), B, C_, H * W, gn.num_groups, float(gn.eps), act, st()), "ap_groupnorm_bwd")
+                else:
+                    dgm = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.weight] else None
+                    dbt = torch.empty(C_, device=dev, dtype=torch.float32) if want[gn.bias] else None
+                    dss = torch.empty_like(ss) if ss is not None else None
+                    N.check(lib.ap_groupnorm_train_bwd(N.ptr(x), N.ptr(gn.weight.detach()), N.ptr(gn.bias.detach()), N.ptr(ss), N.ptr(g),
+                                                       N.ptr(dx), N.ptr(dgm), N.ptr(dbt), N.ptr(dss), tr.gn_ws.data_ptr(),
+                                                       tr.gn_ws.numel(), B, C_, H * W, gn.num_groups, float(gn.eps), act, st()),
+                            "ap_groupnorm_train_bwd")
+                    if dgm is not None:
+                        pgrad[gn.weight] = dgm
+                    if dbt is not None:
+                        pgrad[gn.bias] = dbt
+                    if dss is not None:
+                        grads[id(ss)] = dss
                 acc(x, dx)
             elif kind == "ss":                                    # this block's rows of the concatenated projection's cotangent
                 _, ss, off, n = op
-                g = grads.pop(id(ss), None)
-                if g is None:
-                    continue
                 if id(emb_proj) not in grads:
                     grads[id(emb_proj)] = torch.zeros((B, total), device=dev, dtype=torch.float32)
                 N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(grads[id(emb_proj)]), B, n, 1, n, 0, total, off, st()), "ap_copy_channels")
             elif kind == "drop":
                 _, h, y, draw = op
-                g = grads.pop(id(y), None)
-                if g is None:
-                    continue
-                tr = cfg
+                cfg = tr.cfg
                 dh = torch.empty_like(g)
-                N.check(lib.ap_dropout(N.ptr(g), N.ptr(dh), B, h[0].numel(), tr["p"], tr["seed"], draw, tr["offset"], st()), "ap_dropout")
+                N.check(lib.ap_dropout(N.ptr(g), N.ptr(dh), B, h[0].numel(), cfg["p"], cfg["seed"], draw, cfg["offset"], st()), "ap_dropout")
                 acc(h, dh)
             elif kind == "embcat":
-                g = grads.pop(id(emb_proj), None)
-                if g is None:
-                    continue
                 ws_ = [rb.emb_layers[1].weight for rb in rbs]
                 bs_ = [rb.emb_layers[1].bias for rb in rbs]
                 dW, db = wgrad(g, emb_s, (total, ted) if any(want[w] for w in ws_) else None, any(want[b] for b in bs_),
@@ -633,17 +563,11 @@ class UNetModel(nn.Module):
                 acc(emb_s, d)
             elif kind == "silu":
                 _, xin, y = op
-                g = grads.pop(id(y), None)
-                if g is None:
-                    continue
                 d = torch.empty_like(xin)
                 N.check(lib.ap_silu_bwd(N.ptr(xin), N.ptr(g), N.ptr(d), xin.numel(), st()), "ap_silu_bwd")
                 acc(xin, d)
             elif kind == "attn":
                 _, qkv, att, heads = op
-                g = grads.pop(id(att), None)
-                if g is None:
-                    continue
                 _, C_, H, W = att.shape
                 dqkv = torch.empty_like(qkv)
                 stats = torch.empty(B * heads * H * W * 3, device=dev, dtype=torch.float32)
@@ -652,18 +576,12 @@ class UNetModel(nn.Module):
                 acc(qkv, dqkv)
             elif kind == "up":
                 _, h, up = op
-                g = grads.pop(id(up), None)
-                if g is None:
-                    continue
                 _, C_, H, W = h.shape
                 dh = torch.empty_like(h)
                 N.check(lib.ap_upsample_nearest2x_bwd(N.ptr(g), N.ptr(dh), B * C_, H, W, st()), "ap_upsample_nearest2x_bwd")
                 acc(h, dh)
             elif kind == "cat":
                 _, h, skip, cat = op
-                g = grads.pop(id(cat), None)
-                if g is None:
-                    continue
                 _, C1, H, W = h.shape
                 C2 = skip.shape[1]
                 dh, dsk = torch.empty_like(h), torch.empty_like(skip)
@@ -671,7 +589,23 @@ class UNetModel(nn.Module):
                 N.check(lib.ap_copy_channels(N.ptr(g), N.ptr(dsk), B, C2, H * W, C1 + C2, C1, C2, 0, st()), "ap_copy_channels")
                 acc(h, dh)
                 acc(skip, dsk)
-        return (grads.get(id(x_in)) if want_dx else None), pgrad
+        if tr is None:
+            raise RuntimeError("tape without an input record")
+        return grads.get(id(x_in)) if tr.want_dx else None
+
+
+# tape record kind -> position of the tensor the record produced (the sweep takes that tensor's cotangent)
+_OUT = {"conv": 4, "gn": 5, "ss": 1, "drop": 2, "embcat": 2, "silu": 2, "attn": 2, "up": 2, "cat": 3}
+
+
+class _TrainSweep:
+    """What the reverse sweep needs to leave the parameter cotangents too: which parameters want one ({parameter: bool}) and whether
+    the input does, the dropout configuration of the forward, the concatenated emb_layers projection's input and output, the
+    ap_conv2d_wgrad and ap_groupnorm_train_bwd workspaces sized for this tape -- and where the cotangents go (``pgrad``)."""
+
+    def __init__(self, want, want_dx, cfg, emb_s, emb_proj, wg_ws, gn_ws):
+        self.want, self.want_dx, self.cfg, self.emb_s, self.emb_proj = want, want_dx, cfg, emb_s, emb_proj
+        self.wg_ws, self.gn_ws, self.pgrad = wg_ws, gn_ws, {}
 
 
 class _UNetTrainFn(torch.autograd.Function):
