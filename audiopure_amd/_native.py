@@ -34,6 +34,21 @@ class ApStep(C.Structure):
     _fields_ = [("step", C.c_float), ("ca", C.c_float), ("cb", C.c_float), ("cs", C.c_float), ("draw", C.c_int32)]
 
 
+AP_OPTIM_ADAM, AP_OPTIM_ADAMW, AP_OPTIM_SGD, AP_OPTIM_EMA_ONLY = 0, 1, 2, 3
+AP_OPTIM_MAX_EMA = 4
+
+
+class ApOptimTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p),
+                ("ema", C.c_void_p * AP_OPTIM_MAX_EMA), ("n", C.c_uint64), ("step_size", C.c_float), ("sqrt_bc2", C.c_float)]
+
+
+class ApOptimHyper(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_ema", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("weight_decay", C.c_double), ("momentum", C.c_double),
+                ("ema_rate", C.c_double * AP_OPTIM_MAX_EMA)]
+
+
 _vp, _fp, _u64, _u32, _i, _f, _sz = C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/audiopure.h declares
@@ -170,6 +185,11 @@ SIGNATURES = {
     "ap_dropout": (_i, [_fp, _fp, _i, _i, _f, _u64, _u32, _u64, _vp]),
     "ap_silu_bwd": (_i, [_fp, _fp, _fp, _sz, _vp]),
     "ap_qsample_rows": (_i, [_fp, _fp, _fp, _fp, _fp, _i, _i, _vp]),
+    "ap_optim_slab": (_i, []),
+    "ap_optim_chunk": (_i, []),
+    "ap_optim_step": (_i, [C.POINTER(ApOptimTensor), _i, C.POINTER(ApOptimHyper), _vp]),
+    "ap_optim_sqnorm_workspace_bytes": (_sz, [C.POINTER(_u64), _i]),
+    "ap_optim_sqnorm": (_i, [C.POINTER(_vp), C.POINTER(_u64), _i, _vp, _sz, _vp, _vp]),
 }
 
 _LIB = None

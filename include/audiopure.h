@@ -717,6 +717,63 @@ int ap_silu_bwd(const float *x, const float *dy, float *dx, size_t n, void *stre
  * out[b] = a[b] x0[b] + b[b] z[b]; x0, z, out [B][n], a and b device rows [B]. */
 int ap_qsample_rows(const float *x0, const float *z, const float *a, const float *b, float *out, int B, int n, void *stream);
 
+/* ---- optimizer step (ap_optim.hip).  The reference's trainers end every iteration in torch.optim: Adam with coupled weight decay
+ * (DiffWave_Unconditional/train.py:79, M5/train.py:51, RCNN_KWS/train.py:80, train_speech_commands.py:99), SGD(momentum 0.9,
+ * weight_decay) (train_speech_commands.py:97) and AdamW (improved_diffusion/train_util.py:82); the UNet loop also walks every
+ * parameter for the gradient norm (train_util.py:254-258, one host read per tensor) and for each EMA rate (nn.py:55-65).  These
+ * entry points run all of it over a table of tensors: ceil(n_tensors / ap_optim_slab()) launches per call, the table in the kernel
+ * arguments, no copy, no allocation, no synchronise.  fp32; the formulas are torch.optim's default single-tensor path, element by
+ * element, with the scalars rounded to fp32 once and the roundings of torch's default path on the device (a rounding after each of
+ * its operators, one fma inside add(alpha), lerp, addcmul and addcdiv, correctly rounded sqrt and divide): the results are
+ * torch.optim's bit for bit; no atomics, two runs give equal bits.  Every refusal is -22 with ap_last_error set
+ * before any launch. ---- */
+#define AP_OPTIM_MAX_EMA 4
+enum {
+  AP_OPTIM_ADAM = 0,     /* g += wd p;  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;
+                            p -= step_size m / (sqrt(v) / sqrt_bc2 + eps) */
+  AP_OPTIM_ADAMW = 1,    /* p *= 1 - lr wd first, then AP_OPTIM_ADAM's step with the bare gradient */
+  AP_OPTIM_SGD = 2,      /* g += wd p;  momentum != 0: state1 = momentum state1 + g, g = state1;  p -= lr g   (dampening 0, no Nesterov;
+                            state1 holds zeros before the first step) */
+  AP_OPTIM_EMA_ONLY = 3  /* the EMA copies only: update_ema (nn.py:55-65) on its own; param is read, never written */
+};
+/* One tensor of the table; every pointer a device pointer to n contiguous fp32 elements at any 4-byte offset (16-byte loads and
+ * stores where all of a tensor's pointers are 16-byte aligned, per element otherwise).  grad NULL: the parameter did not take part
+ * in the backward; its state stays and only its EMA copies move (update_ema walks every parameter).  state1 / state2: exp_avg /
+ * exp_avg_sq (Adam, AdamW), momentum_buffer / unused (SGD with momentum != 0; unused without).  ema[k], k < n_ema, after the update
+ * and in the same pass: ema[k] = rate[k] ema[k] + (1 - rate[k]) p_new.  step_size = lr / (1 - beta1^t) and sqrt_bc2 =
+ * sqrt(1 - beta2^t), formed by the caller in double and rounded: per tensor, because a parameter without a grad does not advance
+ * its step count t.  Both unused by AP_OPTIM_SGD and AP_OPTIM_EMA_ONLY. */
+typedef struct ap_optim_tensor {
+  float *param;
+  const float *grad;
+  float *state1, *state2;
+  float *ema[AP_OPTIM_MAX_EMA];
+  uint64_t n;
+  float step_size, sqrt_bc2;
+} ap_optim_tensor;
+/* The launch's hyper-parameters, in double as Python holds them; the library rounds each to fp32 once (1 - beta_i, 1 - lr wd and
+ * 1 - rate formed in double first, as torch's scalar arguments are).  Refused: kind not one of AP_OPTIM_*, n_ema outside
+ * [0, AP_OPTIM_MAX_EMA] (AP_OPTIM_EMA_ONLY: n_ema >= 1), a beta outside [0, 1), a negative lr, eps, weight_decay or momentum, an
+ * ema_rate outside [0, 1], a null param, a null state tensor the kind needs, a null ema[k < n_ema]. */
+typedef struct ap_optim_hyper {
+  int32_t kind;                       /* AP_OPTIM_* */
+  int32_t n_ema;
+  double lr, beta1, beta2, eps, weight_decay, momentum;
+  double ema_rate[AP_OPTIM_MAX_EMA];
+} ap_optim_hyper;
+/* Tensors per launch and elements per workgroup (a tensor of n elements is ceil(n / chunk) workgroups): where the kernel branches. */
+int ap_optim_slab(void);
+int ap_optim_chunk(void);
+/* One step over `tensors` (a host array of n_tensors descriptors; n_tensors = 0 is a no-op). */
+int ap_optim_step(const ap_optim_tensor *tensors, int n_tensors, const ap_optim_hyper *hp, void *stream);
+/* out[0] = sum over the table of g^2 as one device double (the square of train_util.py:254-258's norm): each chunk sums its squares
+ * in fp64 (an fp32 square is exact there) into `workspace`, one last workgroup adds the partials in a fixed order.  grads and n are
+ * host arrays of n_tensors device pointers / element counts; workspace: ap_optim_sqnorm_workspace_bytes(n, n_tensors) bytes, 8-byte
+ * aligned like out.  No host read: the caller reads the double when it needs it. */
+size_t ap_optim_sqnorm_workspace_bytes(const uint64_t *n, int n_tensors);
+int ap_optim_sqnorm(const float *const *grads, const uint64_t *n, int n_tensors, void *workspace, size_t ws_bytes, double *out,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif
