@@ -190,6 +190,10 @@ SIGNATURES = {
     "ap_optim_step": (_i, [C.POINTER(ApOptimTensor), _i, C.POINTER(ApOptimHyper), _vp]),
     "ap_optim_sqnorm_workspace_bytes": (_sz, [C.POINTER(_u64), _i]),
     "ap_optim_sqnorm": (_i, [C.POINTER(_vp), C.POINTER(_u64), _i, _vp, _sz, _vp, _vp]),
+    "ap_class_loss": (_i, [_fp, _vp, _fp, _i, _fp, _fp, _fp, _vp, _vp, _i, _i, _vp]),
+    "ap_mixup_rows": (_i, [_fp, _vp, _fp, _fp, _i, _i, _vp]),
+    "ap_mixup_targets": (_i, [_vp, _vp, _fp, _fp, _i, _i, _vp]),
+    "ap_scale_by_scalar": (_i, [_fp, _fp, _f, _fp, _sz, _vp]),
 }
 
 _LIB = None

@@ -14,7 +14,9 @@ In ``train()`` mode (``train_speech_commands.py:122-153``) the same tape is lowe
 (``lower(module, chw, train=True)``): BatchNorm stays a ``bn`` step on batch statistics (``ap_bn2d_train_fwd`` / ``_bwd``), the plan
 names the module's live parameters, and the reverse sweep also leaves every parameter gradient (``ap_conv2d_wgrad``, ``ap_rowsum``).
 The train step's torch operators are bookkeeping only: one fused increment of the ``num_batches_tracked`` counters per forward and the
-zero fill of each gradient buffer of the sweep.
+zero fill of each gradient buffer of the sweep.  Live dropout (every ``vgg*``, ``wideresnet28_10D``) is a ``drop`` step of that plan on
+the library's counter-based Philox masks (``ap_dropout``) where the caller asks for it (``NativeConvNet.set_dropout``); by default it
+stays a refusal, since those masks are not torch's generator stream.
 """
 from __future__ import annotations
 
@@ -69,7 +71,7 @@ class Val:
 
 @dataclass
 class Step:
-    kind: str                      # conv | affine | add | copy | pool | bn (train plans only)
+    kind: str                      # conv | affine | add | copy | pool | bn, drop (train plans only)
     out: Val = None
     ins: list = field(default_factory=list)
     p: dict = field(default_factory=dict)
@@ -103,11 +105,15 @@ def _need(cond, what: str) -> None:
         raise NotImplementedError("convnet lowering: " + what)
 
 
-def _train_checks(m: nn.Module):
-    """What the train plan does not serve, as ``NotImplementedError`` before anything is traced."""
+def _train_checks(m: nn.Module, dropout: bool = False):
+    """What the train plan does not serve, as ``NotImplementedError`` before anything is traced.  ``dropout``: nn.Dropout is served
+    (a ``drop`` step); nn.Dropout2d and nn.AlphaDropout, whose semantics differ, stay refused."""
     bn_of = {}
     for mod in m.modules():
-        if isinstance(mod, (nn.Dropout, nn.Dropout2d, nn.AlphaDropout)) and mod.p > 0:
+        if dropout and isinstance(mod, nn.modules.dropout._DropoutNd) and not isinstance(mod, nn.Dropout) and mod.p > 0:
+            raise NotImplementedError(f"convnet lowering: live {type(mod).__name__} is not served (the drop step is nn.Dropout's "
+                                      "per-element mask; whole-channel and alpha dropout differ)")
+        if not dropout and isinstance(mod, (nn.Dropout, nn.Dropout2d, nn.AlphaDropout)) and mod.p > 0:
             raise NotImplementedError("convnet lowering: live dropout (nn.Dropout(p > 0) in train() mode) has no kernel")
         if isinstance(mod, nn.modules.batchnorm._BatchNorm):
             _need(mod.affine, "BatchNorm(affine=False) is not served in train() mode")
@@ -116,22 +122,44 @@ def _train_checks(m: nn.Module):
     return bn_of
 
 
-def lower(module: nn.Module, example_chw=(1, 32, 32), train: bool = False) -> Plan:
+class _DropoutAsOneOp:
+    """For the duration of a train-plan trace ``torch.nn.functional.dropout`` -- which nn.Dropout calls too -- is one recognisable
+    ATen operator (``native_dropout``) instead of its CPU decomposition (empty_like, bernoulli_, div_, mul)."""
+
+    def __enter__(self):
+        import torch.nn.functional as F_
+        self.F, self.orig = F_, F_.dropout
+
+        def dropout(input, p=0.5, training=True, inplace=False):
+            _need(not inplace, "in-place dropout is not lowered")
+            return torch.ops.aten.native_dropout(input, float(p), bool(training))[0]
+        F_.dropout = dropout
+
+    def __exit__(self, *exc):
+        self.F.dropout = self.orig
+
+
+def lower(module: nn.Module, example_chw=(1, 32, 32), train: bool = False, dropout: bool = False) -> Plan:
     """Record one forward of `module` on a CPU example [2, C, H, W] and turn it into a Plan: an eval forward with BatchNorm folded
     away, or (``train=True``) a train-mode forward whose plan keeps every BatchNorm as a ``bn`` step on batch statistics and
-    names the module's live parameters and buffers by their state-dict keys instead of cloning them."""
+    names the module's live parameters and buffers by their state-dict keys instead of cloning them.  ``dropout=True`` (train plans
+    only): a live nn.Dropout / F.dropout is a ``drop`` step (``ap_dropout`` on the library's Philox stream, ``draw`` = its ordinal in
+    execution order) instead of a refusal."""
+    import contextlib
     m = copy.deepcopy(module).to("cpu").float()
     m.train(train)
-    bn_of = _train_checks(m) if train else {}
+    dropout = bool(dropout and train)
+    bn_of = _train_checks(m, dropout) if train else {}
     names = {}
     for n_, t in list(m.named_parameters()) + list(m.named_buffers()):
         names[id(t)] = n_
     x = torch.zeros((2,) + tuple(example_chw))
     tape = _Tape()
-    with torch.no_grad(), tape:
+    with torch.no_grad(), (_DropoutAsOneOp() if dropout else contextlib.nullcontext()), tape:
         y = m(x)
     plan = Plan()
     plan.train = train
+    n_drop = 0
     vals: dict[int, Any] = {}         # id(tensor) -> Val | ("param", tensor) | ("paramT", tensor)
     plan.input = plan.new_buf(*example_chw)
     vals[id(x)] = plan.input
@@ -158,7 +186,17 @@ def lower(module: nn.Module, example_chw=(1, 32, 32), train: bool = False) -> Pl
         if op in ("detach", "alias", "clone", "contiguous", "_to_copy", "dropout", "native_dropout"):
             src = args[0]
             if train and op in ("dropout", "native_dropout"):
-                _need(not (args[1] > 0 and (len(args) < 3 or args[2] is None or args[2])), "live dropout (p > 0 in train() mode) has no kernel")
+                live_drop = args[1] > 0 and (len(args) < 3 or args[2] is None or args[2])
+                _need(dropout or not live_drop, "live dropout (p > 0 in train() mode) has no kernel")
+                if live_drop:
+                    v = get(src)
+                    _need(args[1] < 1, "dropout with p = 1 is not served")
+                    _need(isinstance(v, Val) and v.full, "dropout on a channel slice of a wider buffer (coff != 0 or cstride != C) is not served")
+                    o = plan.new_buf(v.C, v.H, v.W)
+                    plan.steps.append(Step("drop", o, [v], dict(p=float(args[1]), draw=n_drop)))
+                    n_drop += 1
+                    vals[id(out[0] if isinstance(out, tuple) else out)] = o
+                    continue
             vals[id(out if not isinstance(out, tuple) else out[0])] = get(src)
         elif op == "convolution":
             xin, w, b, stride, padding, dilation, transposed, _, groups = args[:9]
@@ -415,7 +453,7 @@ class _ConvNetTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, net, tplan, names, *params):
-        out, saved = net._run_train(x, tplan, keep=True)
+        out, saved = net._run_train(x, tplan, keep=True, drop=net._drop_now)
         ctx.net, ctx.tplan, ctx.names, ctx.saved = net, tplan, names, saved
         ctx.save_for_backward(x, *params)                        # (an in-place change of x or a parameter before backward is torch's error;
                                                                  #  the kept input activation may alias x)
@@ -429,8 +467,8 @@ class _ConvNetTrainFn(torch.autograd.Function):
             raise RuntimeError("audiopure_amd NativeConvNet: the train-mode step was already back-propagated (its activations are freed)")
         params = dict(zip(ctx.names, ctx.saved_tensors[1:]))
         want = {n for n, need in zip(ctx.names, ctx.needs_input_grad[4:]) if need}
-        bufs, stats = ctx.saved
-        tr = _TrainSweep(ctx.tplan, params, stats, want, ctx.needs_input_grad[0])
+        bufs, stats, drop = ctx.saved                            # (the dropout stream is kept with the activations: seed and offset)
+        tr = _TrainSweep(ctx.tplan, params, stats, want, ctx.needs_input_grad[0], drop)
         with torch.no_grad():
             dx = ctx.net._input_grad(bufs, g.detach().float().contiguous(), train=tr)
         ctx.saved = None
@@ -441,8 +479,9 @@ class _TrainSweep:
     """What the reverse sweep needs beyond the activations when it runs a train plan: the live parameters by name, each ``bn``
     step's [2][C] batch statistics, which parameters want a gradient, and where those gradients go."""
 
-    def __init__(self, plan, params, stats, want, want_dx):
+    def __init__(self, plan, params, stats, want, want_dx, drop=None):
         self.plan, self.params, self.stats, self.want, self.want_dx = plan, params, stats, want, want_dx
+        self.drop = drop                                         # the forward's dropout stream: dict(seed, offset) or None
         self.grads = {}
 
     def grad_of(self, name):
@@ -457,8 +496,8 @@ class _TrainRun:
     """What the step loop needs to run a train plan: the module's live parameters and buffers by name and the per-plan device images
     (``_train_images``); it leaves each ``bn`` step's [2][C] batch statistics and the counters of the layers that ran."""
 
-    def __init__(self, live, img):
-        self.live, self.img = live, img
+    def __init__(self, live, img, drop=None):
+        self.live, self.img, self.drop = live, img, drop         # drop: this forward's dropout stream, dict(seed, offset) or None
         self.stats, self.counters = {}, []
 
 
@@ -500,7 +539,7 @@ class NativeConvNet(nn.Module):
 
     def __getstate__(self):                    # device images / packed weights are rebuilt on demand, never pickled
         d = dict(self.__dict__)
-        for k in ("_dev_weights", "_packed", "_dev", "_bwd_packed", "_bwd_key", "_zero_vec", "_train_plan", "_train_chw", "_train_bufs"):
+        for k in ("_dev_weights", "_packed", "_dev", "_bwd_packed", "_bwd_key", "_zero_vec", "_train_plan", "_train_chw", "_train_bufs", "_train_drop", "_drop_now"):
             d.pop(k, None)
         return d
 
@@ -553,7 +592,7 @@ class NativeConvNet(nn.Module):
     def forward(self, x):
         """A module that ``lower_classifier`` wrapped on sight (``input_chw=None``) is only KNOWN to contain Conv2d layers.
         What the reference's scripts would have done with it stays possible in three named cases -- ``train()`` mode where the
-        train plan has no kernel (live dropout, ``affine=False``, ...) or the module is not on the device, a CPU module fed CPU tensors, and a trace that meets an operator the library has no
+        train plan has no kernel (live dropout without ``set_dropout``, ``affine=False``, ...) or the module is not on the device, a CPU module fed CPU tensors, and a trace that meets an operator the library has no
         kernel for (``lower`` raises ``NotImplementedError``; any other failure of the lowering propagates) -- each said once with
         a ``RuntimeWarning`` and each an error under ``AUDIOPURE_STRICT=1``.  An explicitly constructed
         ``NativeConvNet(module, chw)`` lowers in ``__init__`` and raises there instead."""
@@ -564,7 +603,9 @@ class NativeConvNet(nn.Module):
                     tplan = self._train_plan_for(x)
                 except NotImplementedError as e:                 # live dropout, affine=False, ...: no kernel -- today's announced route
                     if strict():
-                        raise N.NativeError(f"{type(self.module).__name__}: train() mode not lowered ({e}); AUDIOPURE_STRICT=1 forbids "
+                        hint = ("; set_dropout('philox') opts in to the library's own Philox masks" if ("dropout" in str(e) or "bernoulli_" in str(e))
+                                and self._dropout is None else "")   # (F.dropout traces as empty_like, bernoulli_, div_, mul)
+                        raise N.NativeError(f"{type(self.module).__name__}: train() mode not lowered ({e}{hint}); AUDIOPURE_STRICT=1 forbids "
                                             "running the caller's module on PyTorch operators") from e
                 else:
                     return self._forward_train(x, tplan)         # batch-statistics BatchNorm and parameter gradients on the HIP library
@@ -662,6 +703,11 @@ class NativeConvNet(nn.Module):
                 if nbt is not None:
                     tr.counters.append(nbt)
                 tr.stats[i] = stat
+            elif s.kind == "drop":                               # the mask is a function of (seed, draw, sample, element): nothing is kept
+                v = s.ins[0]
+                assert o.full and v.full and tr.drop is not None
+                N.check(lib.ap_dropout(N.ptr(buf(v)), N.ptr(ob), B, v.C * v.H * v.W, p["p"], tr.drop["seed"], p["draw"], tr.drop["offset"],
+                                       st_), "ap_dropout")
             elif s.kind == "affine":
                 v = s.ins[0]
                 assert o.full and (tr is None or p["sk"] is None)    # a train plan's affine steps are bare ReLUs (lower())
@@ -691,12 +737,43 @@ class NativeConvNet(nn.Module):
     _train_chw = None
     _train_bufs = None                         # per conv step: the packed forward / backward weight images, written anew every step
 
+    _dropout = None                            # set_dropout's spec
+    _train_drop = False                        # whether the cached train plan was lowered with dropout=True
+    _drop_now = None                           # the dropout stream of the train forward that is running
+
+    def set_dropout(self, spec):
+        """How a live nn.Dropout / F.dropout of the wrapped module runs in ``train()`` mode.
+        ``None`` (default): it does not -- the train plan refuses it (an error under AUDIOPURE_STRICT=1, else the announced PyTorch route).
+        ``"philox"``: the library's counter-based Philox masks (``ap_dropout``; NOT torch's generator stream); every train-mode forward
+        draws a 64-bit seed from torch's CPU generator, so ``torch.manual_seed`` reproduces a run; sample offset 0.
+        ``("philox", seed, sample_offset)``: a fixed stream; ``sample_offset`` is the global index of the batch's first sample (a
+        sharded batch).  Eval mode is unaffected: dropout is inert there."""
+        if spec is not None and spec != "philox":
+            if not (isinstance(spec, (tuple, list)) and len(spec) == 3 and spec[0] == "philox"):
+                raise ValueError('set_dropout: None, "philox" or ("philox", seed, sample_offset)')
+            spec = ("philox", int(spec[1]) & ((1 << 64) - 1), int(spec[2]))
+            if spec[2] < 0:
+                raise ValueError("set_dropout: sample_offset must not be negative")
+        self._dropout = spec
+        return self
+
+    def _dropout_stream(self):
+        """-> dict(seed, offset) of one train-mode forward, or None where dropout is not opted in."""
+        if self._dropout is None:
+            return None
+        if self._dropout == "philox":
+            w = torch.randint(0, 1 << 32, (2,), dtype=torch.int64)   # torch's CPU generator: torch.manual_seed reproduces a step
+            return dict(seed=(int(w[0]) << 32) | int(w[1]), offset=0)
+        return dict(seed=self._dropout[1], offset=self._dropout[2])
+
     def _train_plan_for(self, x):
         if x.dim() != 4:
             raise ValueError(f"expected [B, C, H, W], got {tuple(x.shape)}")
         chw = tuple(x.shape[1:])
-        if self._train_plan is None or self._train_chw != chw:
-            self._train_plan, self._train_chw, self._train_bufs = lower(self.module, chw, train=True), chw, None
+        drop = self._dropout is not None
+        if self._train_plan is None or self._train_chw != chw or self._train_drop != drop:     # cached per setting: toggling re-lowers
+            self._train_plan = None
+            self._train_plan, self._train_chw, self._train_drop, self._train_bufs = lower(self.module, chw, train=True, dropout=drop), chw, drop, None
         return self._train_plan
 
     def _live_tensors(self):
@@ -712,9 +789,10 @@ class NativeConvNet(nn.Module):
         pnames = tuple(n for n, _ in self.module.named_parameters())
         if any(live[n].dtype != torch.float32 or not live[n].is_contiguous() for n in pnames):
             raise N.NativeError("NativeConvNet: train() mode needs contiguous float32 parameters")
+        self._drop_now = self._dropout_stream() if any(s.kind == "drop" for s in tplan.steps) else None
         if torch.is_grad_enabled() and (x.requires_grad or any(live[n].requires_grad for n in pnames)):
             return _ConvNetTrainFn.apply(x, self, tplan, pnames, *[live[n] for n in pnames])
-        return self._run_train(x, tplan, keep=False)[0]          # no_grad: the statistics move, nothing is kept
+        return self._run_train(x, tplan, keep=False, drop=self._drop_now)[0]   # no_grad: the statistics move (and the same masks apply), nothing is kept
 
     def _train_images(self, tplan, dev):
         """Device buffers for the packed weight images of every conv step (forward and transposed), the flip scratch and the
@@ -737,8 +815,8 @@ class NativeConvNet(nn.Module):
                                 bn_ws=torch.empty(lib.ap_bn2d_train_workspace_bytes(cmax), device=dev, dtype=torch.uint8))
         return self._train_bufs
 
-    def _run_train(self, x, tplan, keep):
-        """-> (scores, (every buffer of the plan, {bn step: its [2][C] batch statistics}) or None).  Updates running_mean /
+    def _run_train(self, x, tplan, keep, drop=None):
+        """-> (scores, (every buffer of the plan, {bn step: its [2][C] batch statistics}, the dropout stream) or None).  Updates running_mean /
         running_var in place (the kernels do) and increments num_batches_tracked, as nn.BatchNorm2d does (also under no_grad).  The
         counters are int64 bookkeeping and move by one fused torch call per step, the only torch operator in it; a
         BatchNorm(momentum=None) additionally reads its counter on the host (one device-to-host copy per such layer and step), as
@@ -747,11 +825,11 @@ class NativeConvNet(nn.Module):
             raise ValueError(f"expected [B, {self._train_chw}], got {tuple(x.shape)}")
         dev = x.device
         N.use_conv_workspace(dev)
-        tr = _TrainRun(self._live_tensors(), self._train_images(tplan, dev))
+        tr = _TrainRun(self._live_tensors(), self._train_images(tplan, dev), drop)
         out, bufs = self._execute(x, tplan, tr)
         if tr.counters:                                          # num_batches_tracked += 1, every BatchNorm's int64 counter in one
             torch._foreach_add_(tr.counters, 1)                  # fused torch call: the step's only torch operator
-        return out, ((bufs, tr.stats) if keep else None)
+        return out, ((bufs, tr.stats, drop) if keep else None)
 
     # ---- input gradient (SURVEY section 8 f-1 for the spectrogram classifiers) ------------------------------------
     def _prepare_backward(self):
@@ -866,6 +944,12 @@ class NativeConvNet(nn.Module):
                         "ap_bn2d_train_bwd")
                 if want:
                     acc(tmp, o.C, o.H * o.W, o.C, 0, v)
+            elif s.kind == "drop":                               # the forward's call on the cotangent: the same mask, the same scale
+                v = s.ins[0]
+                tmp = torch.empty((B, o.C, o.H, o.W), device=dev, dtype=torch.float32)
+                N.check(lib.ap_dropout(N.ptr(gbuf(o.buf)), N.ptr(tmp), B, o.C * o.H * o.W, p["p"], train.drop["seed"], p["draw"],
+                                       train.drop["offset"], st_), "ap_dropout")
+                acc(tmp, o.C, o.H * o.W, o.C, 0, v)
             elif s.kind == "affine":
                 v = s.ins[0]
                 dy = masked(o, p["relu"])

@@ -774,6 +774,32 @@ size_t ap_optim_sqnorm_workspace_bytes(const uint64_t *n, int n_tensors);
 int ap_optim_sqnorm(const float *const *grads, const uint64_t *n, int n_tensors, void *workspace, size_t ws_bytes, double *out,
                     void *stream);
 
+/* ---- loss head: what train_speech_commands.py:131-163 runs between model(inputs) and optimizer.step().  Plain fp32 (expf / logf,
+ * correctly rounded divide), no atomics, nothing allocated; every refusal is -22 with ap_last_error set before any launch. ---- */
+/* Loss of B rows of K scores, the seed of loss.backward(), the predictions and the count of correct ones, in two launches (one wave
+ * per row; one workgroup that adds the B row losses in fp64 in index order and counts: two runs give equal bits).
+ *   mode 0  nn.CrossEntropyLoss():  row = logsumexp(in) - in[y] (row maximum subtracted first), loss = mean, din = (softmax - onehot) / B
+ *   mode 1  mixup_cross_entropy_loss(in, soft) (mixup.py:17-29): p = softmax(in), row = -sum_i soft_i log(clamp(p_i, 1e-5, 1)),
+ *           loss = sum / B, din_j = (-soft_j m_j + p_j sum_i soft_i m_i) / B with m_i = [1e-5 <= p_i <= 1], autograd's clamp
+ *   mode 2  F.nll_loss on log-probabilities:  row = -in[y], din = -1 / B at y and 0 elsewhere
+ * labels int64 [B] (modes 0, 2; in mode 1 optional, for n_correct only), soft [B][K] (mode 1).  loss_rows [B] and loss [1] are
+ * written always; din [B][K], pred int64 [B] (the LOWEST index of the row maximum of `in`) and n_correct int64 [1] (#{pred ==
+ * labels}; needs labels and pred) may each be NULL.  A label outside [0, K) makes its row's loss and din row NaN; nothing is read out
+ * of bounds.  1 <= K <= 4096, 1 <= B <= 65535; din must not overlap in or soft.  No ignore_index, class weights or label smoothing. */
+int ap_class_loss(const float *in, const int64_t *labels, const float *soft, int mode, float *loss_rows, float *loss, float *din,
+                  int64_t *pred, int64_t *n_correct, int B, int K, void *stream);
+/* mixup (mixup.py:40-52) on device tensors, with torch's fp32 rounding sequence -- omw = fl(1 - w), fl(fl(w a) + fl(omw c)), never an
+ * fma -- so the bits are those of `weight * x1 + (1 - weight) * x2`:
+ *   ap_mixup_rows     out[b] = w[b] x[b] + (1 - w[b]) x[index[b]], rows of n elements; out overlapping x is refused; an index outside
+ *                     [0, B) writes NaN to that row
+ *   ap_mixup_targets  out[b] = w[b] onehot(labels[b]) + (1 - w[b]) onehot(labels[index[b]]), [B][K]; an index or label out of range
+ *                     writes NaN to that row */
+int ap_mixup_rows(const float *x, const int64_t *index, const float *weight, float *out, int B, int n, void *stream);
+int ap_mixup_targets(const int64_t *labels, const int64_t *index, const float *weight, float *out, int B, int K, void *stream);
+/* out[i] = x[i] * fl(g[0] * factor) with g a DEVICE scalar (g NULL: x[i] * factor): din times the upstream cotangent of the scalar
+ * loss without a host read.  out may be x. */
+int ap_scale_by_scalar(const float *x, const float *g, float factor, float *out, size_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,8 +139,9 @@ class _WideBlock(nn.Module):
     """models/wideresnet.py:16-41 -- pre-activation pair of 3x3s; when the width changes the activated input also feeds the 1x1
     `convShortcut`, otherwise the raw input is the identity branch."""
 
-    def __init__(self, cin, cout, stride):
+    def __init__(self, cin, cout, stride, drop_rate=0.0):
         super().__init__()
+        self.drop_rate = drop_rate
         self.bn1, self.conv1 = _bn(cin), _conv(cin, cout, 3, stride)
         self.bn2, self.conv2 = _bn(cout), _conv(cout, cout, 3)
         if cin != cout:
@@ -149,7 +150,10 @@ class _WideBlock(nn.Module):
 
     def forward(self, x):
         a = F.relu(self.bn1(x))
-        y = self.conv2(F.relu(self.bn2(self.conv1(a))))
+        y = F.relu(self.bn2(self.conv1(a)))
+        if self.drop_rate > 0:                                   # models/wideresnet.py:35-38: between the second ReLU and conv2
+            y = F.dropout(y, p=self.drop_rate, training=self.training)
+        y = self.conv2(y)
         return (self.convShortcut(a) if self.project else x) + y
 
 
@@ -163,15 +167,15 @@ class _Stack(nn.Module):
 
 
 class WideResNet28_10(nn.Module):
-    """models/wideresnet.py:55-92, depth 28 / widen 10 / no dropout: 3x3 stem (16), three stacks of four blocks (160, 320, 640),
-    BN-ReLU, 8 x 8 average pool, fc."""
+    """models/wideresnet.py:55-92, depth 28 / widen 10: 3x3 stem (16), three stacks of four blocks (160, 320, 640),
+    BN-ReLU, 8 x 8 average pool, fc.  ``drop_rate`` (0.3: wideresnet28_10D) is each block's F.dropout; it adds no state-dict key."""
 
-    def __init__(self, num_classes=10, in_channels=1, depth=28, widen=10):
+    def __init__(self, num_classes=10, in_channels=1, depth=28, widen=10, drop_rate=0.0):
         super().__init__()
         n, w = (depth - 4) // 6, [16, 16 * widen, 32 * widen, 64 * widen]
         self.conv1 = _conv(in_channels, w[0], 3)
         for s in (1, 2, 3):
-            setattr(self, f"block{s}", _Stack([_WideBlock(w[s - 1] if i == 0 else w[s], w[s], (1 if s == 1 else 2) if i == 0 else 1)
+            setattr(self, f"block{s}", _Stack([_WideBlock(w[s - 1] if i == 0 else w[s], w[s], (1 if s == 1 else 2) if i == 0 else 1, drop_rate)
                                                for i in range(n)]))
         self.bn1 = _bn(w[3])
         self.fc = nn.Linear(w[3], num_classes)
