@@ -213,6 +213,17 @@ int launch_resblock_split(ap_ctx *ctx, int layer, const float *hin, const float 
                           int accumulate, int B, int L, hipStream_t st);
 int prepare_bwd_f32(ap_ctx *ctx, hipStream_t st);                // ap_ctx_prepare_backward, per precision (allocate + pack + synchronise)
 int prepare_bwd_bf16(ap_ctx *ctx, hipStream_t st);
+// ap_conv_w3.hip: 3 x 3 / stride 1 / pad 1 / ungrouped layers in F(2,3) form along W (which layers: ap_conv_plan.h)
+int launch_conv_pack_w3(const float *w, const float *scale, float *out, int Cout, int Cin, hipStream_t st);
+int launch_conv_w3(const float *x, const float *wimg, const float *bias, const float *res, float *out, int B, int Cin, int H, int W,
+                   int Cout, int relu, int x_cstride, int x_coff, int o_cstride, int o_coff, hipStream_t st, int splits = 1, float *part = nullptr);
+#ifdef AP_TOOLS
+// tools/csrc/ap_conv_p1.hip (tools library only): pointwise layers of the high-resolution maps as an LDS-free streaming GEMM on the
+// family's A-fragment image -- round 6's attempt at VERDICT r5 item 5a, measured slower than the 128 x 64 tiles (profiles/r6_conv_pointwise_streaming_ab.txt)
+bool conv_p1_serves(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups);
+int launch_conv_p1(const float *x, const float *afrag, const float *bias, const float *res, float *out, int B, int Cin, int H, int W, int Cout,
+                   int relu, int x_cstride, int x_coff, int o_cstride, int o_coff, size_t abytes, hipStream_t st);   // 1: not served (tensor too large)
+#endif
 int launch_m5(ap_m5 *m, const float *x, float *logprobs, int B, int L, hipStream_t st);
 int launch_m5_bwd(ap_m5 *m, const float *x, const float *dlogp, float *dx, int B, int L, hipStream_t st);
 int launch_m5_fold(ap_m5 *m, const float *blob, float bn_eps, hipStream_t st);

@@ -12,6 +12,7 @@
 // pre-transformed A fragments streamed L2 -> registers, epilogue = output transform + bias + residual + ReLU with one 8-byte
 // store per (row, pair).  Transformed weights are computed in double at pack time.
 #include "ap_common.h"
+#include "ap_conv_plan.h"   // conv_w3_serves / _elems / _rt / _tiles / _worth / _splits: the pure predicates of this kernel
 
 namespace ap {
 
@@ -19,35 +20,6 @@ namespace {
 constexpr int ZSW_ = 36;                  // floats per column row of a 32-k chunk image
 constexpr unsigned FRAGW_ = 64 * 16;      // bytes of one row tile's fragment of a k-group
 }  // namespace
-
-bool conv_w3_serves(int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups) {
-  return kh == 3 && kw == 3 && stride == 1 && pad == 1 && groups == 1 && Cin % 32 == 0 && Cout % 128 == 0 && (W & 1) == 0 && W >= 2 &&
-         H >= 1;
-}
-size_t conv_w3_elems(int Cout, int Cin) { return (size_t)4 * Cout * Cin * 3; }
-// persistent one-workgroup-per-CU kernel: worth it from two tiles per CU on (measured at B = 256: the UNet's 32 x 32 and 16 x 16 maps
-// 1.15-1.36 x faster than the direct kernels, its 8 x 8 / 4 x 4 maps -- 128 / 32 tiles -- 1.15-3 x slower: those keep the direct kernels)
-long long conv_w3_tiles(int B, int H, int W, int Cout) {
-  const int rt = Cout % 256 == 0 ? 2 : 1, ncol = rt == 2 ? 64 : 128;
-  const long long npairs = (long long)B * H * (W / 2);
-  return (long long)(Cout / (128 * rt)) * ((npairs + ncol - 1) / ncol);
-}
-bool conv_w3_worth(int B, int H, int W, int Cout) { return conv_w3_tiles(B, H, W, Cout) >= 512; }
-// K slices for a layer with too few tiles (the UNet's 8 x 8 and 4 x 4 maps: 128 / 32 tiles): each slice sums its share of the
-// (ky, channel-block) chunks and writes its TRANSFORMED partial outputs (the output transform is linear) to the caller's
-// workspace; the conv launcher's reduce kernel adds the slices in order (deterministic), then bias / residual / ReLU.
-// 0: not worth it (under 32 tiles, or fewer than 3 chunks per slice)
-int conv_w3_splits(int B, int Cin, int H, int W, int Cout, size_t ws_bytes) {
-  const long long t = conv_w3_tiles(B, H, W, Cout);
-  if (t >= 512 || t < 32) return 0;
-  const int nch = 3 * (Cin / 32);
-  int S = 2;
-  while (S < 8 && t * S < 512) S *= 2;
-  while (S > 1 && (nch / S < 3 || (size_t)S * B * Cout * H * W * sizeof(float) > ws_bytes)) S /= 2;
-  return S > 1 ? S : 0;
-}
-// rows per workgroup: 256 (RT = 2 row tiles per wave) where Cout allows it, else 128 (RT = 1, four column tiles per wave)
-static int conv_w3_rt(int Cout) { return Cout % 256 == 0 ? 2 : 1; }
 
 // image: [row block][wave 4][chunk 3 Cin/32][k-group 4][product 4][row tile RT][lane 64][4]; row = 128 RT rb + 32 RT wave + 32 rt + i;
 // chunk = ky (Cin / 32) + cb; k = input channel 32 cb + 8 kg + 4 hh + e

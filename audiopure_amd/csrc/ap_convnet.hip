@@ -7,6 +7,7 @@
 // ([k][m] weights pre-transposed at plan time, [k][n] im2col gather), register-prefetched one chunk ahead.
 // Epilogue fuses the folded-BN bias, an optional residual tensor and ReLU.
 #include "ap_common.h"
+#include "ap_conv_plan.h"
 
 namespace ap {
 
@@ -934,125 +935,48 @@ __global__ void pool2d_kernel(const float *__restrict__ x, float *__restrict__ y
 
 using namespace ap;
 
+// which kernel serves a layer: ap_conv_plan.h (conv_plan), on these thresholds
 #ifdef AP_TOOLS
-static int g_conv_no_frag = 0;     // ap_debug_conv_path(1): timing A/B against the LDS-staged 128 x 128 kernel
-static long long g_conv_frag_min_tiles = 512;   // below two 128 x 128 tiles per CU the 128 x 64 variant wins (swept)
-static int g_conv_wide_1x1 = 0;               // ap_debug_conv_path(2): pointwise layers on 128 x 128 tiles again (A/B)
-static int g_conv_force = 0;                  // ap_debug_conv_path(4..7): every streamed-weight layer on 128x128 / 128x64 / 64x64 / 64x128 tiles; 8: off
-static int g_conv_w3 = 1;                     // ap_debug_conv_w3(on, min_pairs): the F(2,3) kernel for the layers it serves / the direct kernels
-static long long g_conv_w3_min_pairs = 0;
-static int g_conv_w3_split = 1;               // ap_debug_conv_w3(on + 4 * nosplit, ..): K slices for the low-resolution maps on / off
+static ConvTune g_conv_tune;
 extern "C" int ap_debug_conv_w3(int on, int min_pairs) {
-  g_conv_w3 = on & 3;
-  g_conv_w3_split = (on & 4) ? 0 : 1;
-  g_conv_w3_min_pairs = min_pairs;
+  g_conv_tune.w3 = on & 3; g_conv_tune.w3_split = (on & 4) ? 0 : 1;
+  g_conv_tune.w3_min_pairs = min_pairs;
   return 0;
 }
-static int g_conv_p1 = 0;                     // ap_debug_conv_p1(1): the LDS-free pointwise kernel of tools/csrc/ap_conv_p1.hip for the layers it serves (A/B: measured slower)
-extern "C" int ap_debug_conv_p1(int on) {
-  g_conv_p1 = on;
-  return 0;
-}
-static long long g_conv_splitk_t2 = 384;      // ap_debug_conv_splitk: split-K is taken below this many half-tiles (2 x 128 x 128 tiles)
-static int g_conv_splitk_cap = 768;           // ... and slices are doubled while tiles x slices stays below this
-extern "C" int ap_debug_conv_splitk(int t2, int cap) {
-  g_conv_splitk_t2 = t2;
-  g_conv_splitk_cap = cap;
-  return 0;
-}
+extern "C" int ap_debug_conv_p1(int on) { g_conv_tune.p1 = on; return 0; }
+extern "C" int ap_debug_conv_splitk(int t2, int cap) { g_conv_tune.splitk_t2 = t2; g_conv_tune.splitk_cap = cap; return 0; }
 extern "C" int ap_debug_conv_path(int no_frag) {
-  if (no_frag >= 16) g_conv_frag_min_tiles = no_frag;   // >= 16: set the tile-count threshold of the streamed-weight kernel
-  else if (no_frag >= 4 && no_frag <= 8) g_conv_force = no_frag == 8 ? 0 : no_frag;
-  else if (no_frag == 2 || no_frag == 3) g_conv_wide_1x1 = no_frag == 2;   // 2 / 3: pointwise layers on 128 x 128 tiles / back on 128 x 64
-  else g_conv_no_frag = no_frag;
+  if (no_frag >= 16) g_conv_tune.frag_min_tiles = no_frag;   // >= 16: set the tile-count threshold of the streamed-weight kernel
+  else if (no_frag >= 4 && no_frag <= 8) g_conv_tune.force = no_frag == 8 ? 0 : no_frag;
+  else if (no_frag == 2 || no_frag == 3) g_conv_tune.wide_1x1 = no_frag == 2;   // 2 / 3: pointwise layers on 128 x 128 tiles / back on 128 x 64
+  else g_conv_tune.no_frag = no_frag;
   return 0;
 }
 #else
-static constexpr int g_conv_no_frag = 0;
-static constexpr long long g_conv_frag_min_tiles = 512;   // below two 128 x 128 tiles per CU the 128 x 64 variant wins (swept)
-static constexpr int g_conv_wide_1x1 = 0;
-static constexpr long long g_conv_splitk_t2 = 384;
-static constexpr int g_conv_splitk_cap = 768;
-static constexpr int g_conv_w3 = 1;
-static constexpr long long g_conv_w3_min_pairs = 0;
-static constexpr int g_conv_w3_split = 1;
+static constexpr ConvTune g_conv_tune;
 #endif
-
-#ifdef AP_TOOLS
-// tools/csrc/ap_conv_p1.hip (tools library only): pointwise layers of the high-resolution maps as an LDS-free streaming GEMM on the
-// family's A-fragment image -- round 6's attempt at VERDICT r5 item 5a, measured slower than the 128 x 64 tiles (profiles/r6_conv_pointwise_streaming_ab.txt)
-namespace ap {
-bool conv_p1_serves(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups);
-int launch_conv_p1(const float *x, const float *afrag, const float *bias, const float *res, float *out, int B, int Cin, int H, int W, int Cout,
-                   int relu, int x_cstride, int x_coff, int o_cstride, int o_coff, size_t abytes, hipStream_t st);   // 1: not served (tensor too large)
-}
-#endif
-
-// ap_conv_w3.hip: 3 x 3 / stride 1 / pad 1 / ungrouped layers in F(2,3) form along W; their transformed-weight image is the LAST image
-namespace ap {
-bool conv_w3_serves(int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups);
-bool conv_w3_worth(int B, int H, int W, int Cout);
-int conv_w3_splits(int B, int Cin, int H, int W, int Cout, size_t ws_bytes);
-size_t conv_w3_elems(int Cout, int Cin);
-int launch_conv_pack_w3(const float *w, const float *scale, float *out, int Cout, int Cin, hipStream_t st);
-int launch_conv_w3(const float *x, const float *wimg, const float *bias, const float *res, float *out, int B, int Cin, int H, int W,
-                   int Cout, int relu, int x_cstride, int x_coff, int o_cstride, int o_coff, hipStream_t st, int splits = 1, float *part = nullptr);
-}
-static bool conv_has_w3(int Cout, int Cin_g, int kh, int kw, int groups) {
-  return conv_w3_serves(Cin_g, 4, 4, Cout, kh, kw, 1, 1, groups);      // the weight-side conditions (kernel 3 x 3, ungrouped, Cin % 32, Cout % 128)
-}
-
-// layers the streamed-weight kernel serves carry a second image behind the first
-static bool conv_has_frag(int Cout, int Cin_g, int groups) { return Cin_g % 16 == 0 && Cout / groups >= 64; }
-static size_t conv_frag_elems(int Cout, int Cin_g, int kh, int kw, int groups) {
-  const int Mg = Cout / groups;
-  return (size_t)groups * ((Mg + 31) / 32) * 32 * Cin_g * kh * kw;
-}
-
-// third image (3 x bf16 per weight = 1.5 floats), rounded up to whole float4s
-static size_t conv_split_floats(int Cout, int Cin_g, int kh, int kw, int groups) {
-  return (conv_frag_elems(Cout, Cin_g, kh, kw, groups) * 3 / 2 + 3) & ~(size_t)3;
-}
-
-// fourth image (2 x fp16 per weight = 1 float)
-static size_t conv_splith_floats(int Cout, int Cin_g, int kh, int kw, int groups) {
-  return (conv_frag_elems(Cout, Cin_g, kh, kw, groups) + 3) & ~(size_t)3;
-}
 
 extern "C" size_t ap_conv2d_packed_elems(int Cout, int Cin_g, int kh, int kw, int groups) {
   if (Cout < 1 || Cin_g < 1 || kh < 1 || kw < 1 || groups < 1 || Cout % groups) return 0;
-  size_t n = (size_t)Cout * Cin_g * kh * kw;
-  if (conv_has_frag(Cout, Cin_g, groups))
-    n = ((n + 3) & ~(size_t)3) + conv_frag_elems(Cout, Cin_g, kh, kw, groups) + conv_split_floats(Cout, Cin_g, kh, kw, groups) +
-        conv_splith_floats(Cout, Cin_g, kh, kw, groups);
-  if (conv_has_w3(Cout, Cin_g, kh, kw, groups)) n = ((n + 3) & ~(size_t)3) + conv_w3_elems(Cout, Cin_g);
-  return n;
+  return conv_images(Cout, Cin_g, kh, kw, groups).total;
 }
-// offset (floats) of the F(2,3) image inside a packed weight buffer
-static size_t conv_w3_offset(int Cout, int Cin_g, int kh, int kw, int groups) {
-  return ((ap_conv2d_packed_elems(Cout, Cin_g, kh, kw, groups) - conv_w3_elems(Cout, Cin_g)));
-}
-
 extern "C" int ap_conv2d_pack(const float *w, const float *scale, float *wT, int Cout, int Cin_g, int kh, int kw,
                               int groups, void *stream) {
   if (!w || !wT || Cout < 1 || Cin_g < 1 || groups < 1 || Cout % groups) { set_error("ap_conv2d_pack: bad argument"); return -22; }
   const int Kg = Cin_g * kh * kw;
-  size_t n = (size_t)Cout * Kg;
+  const size_t n = (size_t)Cout * Kg;
+  const ConvImages im = conv_images(Cout, Cin_g, kh, kw, groups);
   conv_pack_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, scale, wT, Cout, Kg, groups);
-  if (conv_has_frag(Cout, Cin_g, groups)) {
-    const size_t nf = conv_frag_elems(Cout, Cin_g, kh, kw, groups), n4 = (n + 3) & ~(size_t)3;   // 16-B aligned images
-    conv_pack_frag_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, (hipStream_t)stream>>>(w, scale, wT + n4, Cout, Cin_g,
-                                                                                       kh * kw, groups);
-    conv_pack_split_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        w, scale, reinterpret_cast<__bf16 *>(wT + n4 + nf), Cout, Cin_g, kh * kw, groups);
-    conv_pack_splith_kernel<<<(unsigned)((nf + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        w, scale, reinterpret_cast<_Float16 *>(wT + n4 + nf + conv_split_floats(Cout, Cin_g, kh, kw, groups)), Cout, Cin_g,
-        kh * kw, groups);
+  if (im.has_frag) {
+    const unsigned nb = (unsigned)((im.frag_elems + 255) / 256);
+    conv_pack_frag_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(w, scale, wT + im.frag, Cout, Cin_g, kh * kw, groups);
+    conv_pack_split_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(w, scale, reinterpret_cast<__bf16 *>(wT + im.split), Cout, Cin_g, kh * kw,
+                                                                groups);
+    conv_pack_splith_kernel<<<nb, 256, 0, (hipStream_t)stream>>>(w, scale, reinterpret_cast<_Float16 *>(wT + im.splith), Cout, Cin_g,
+                                                                 kh * kw, groups);
   }
-  if (conv_has_w3(Cout, Cin_g, kh, kw, groups)) {
-    int rc = launch_conv_pack_w3(w, scale, wT + conv_w3_offset(Cout, Cin_g, kh, kw, groups), Cout, Cin_g, (hipStream_t)stream);
-    if (rc) return rc;
-  }
+  if (im.has_w3)
+    if (const int rc = launch_conv_pack_w3(w, scale, wT + im.w3, Cout, Cin_g, (hipStream_t)stream)) return rc;
   AP_HIP(hipGetLastError());
   return 0;
 }
@@ -1064,13 +988,11 @@ struct ConvProf {
   bool on = false;
   std::vector<hipEvent_t> ev;                 // (start, stop) pairs
   std::vector<double> flop;                   // per recorded launch
-  std::vector<int> cls;                       // kernel class per recorded launch: 0 big2<128,128>, 1 big2<64,128>, 2 big2<128,64>,
-  size_t used = 0;                            //   3 split / fp16-split, 4 big (no fragment image), 5 generic
+  std::vector<int> cls;                       // kernel class per recorded launch: conv_class (ap_conv_plan.h) -- 0 / 1 / 2 streamed-weight
+  size_t used = 0;                            //   128x128 / 64x128 / 128x64, 64x64 and split-K, 3 split operands, 4 LDS-staged, 5 generic / few, 6 F(2,3), 7 tools
   std::vector<int> shape;                     // 9 ints per recorded launch: B Cin H W Cout kh kw stride groups
+  void reset() { used = 0; flop.clear(); cls.clear(); shape.clear(); }   // (the events are kept and reused)
 } g_cprof;
-int conv2d_fwd_impl(const float *x, const float *wT, const float *bias, const float *res, float *out, int B, int Cin, int H,
-                    int W, int Cout, int kh, int kw, int stride, int pad, int groups, int relu, int x_cstride, int x_coff,
-                    void *stream, int *cls, int o_cstride = 0, int o_coff = 0);
 }  // namespace
 
 // Split-K partial sums live in a caller-owned device buffer (no allocation inside the library): without one, or with one
@@ -1107,10 +1029,7 @@ extern "C" int ap_conv2d_set_workspace(float *ws, size_t bytes) {
 
 extern "C" int ap_conv_profile_enable(int enable) {
   g_cprof.on = enable != 0;
-  g_cprof.used = 0;
-  g_cprof.flop.clear();
-  g_cprof.cls.clear();
-  g_cprof.shape.clear();
+  g_cprof.reset();
   return 0;
 }
 
@@ -1138,44 +1057,119 @@ extern "C" int ap_conv_profile_read(double *ms_by_class, double *flop_by_class, 
     flop_by_class[g_cprof.cls[i]] += g_cprof.flop[i];
     launches_by_class[g_cprof.cls[i]] += 1;
   }
-  g_cprof.used = 0;
-  g_cprof.flop.clear();
-  g_cprof.cls.clear();
-  g_cprof.shape.clear();
+  g_cprof.reset();
   return 0;
 }
 
+namespace {
+// one helper per kernel family: the plan's (tile, form) -> the template instantiation.  Exactly the forms conv_plan asks for are
+// listed (the pointer form never stages pointwise; 64-row tiles do so only as a forced tile of the tools build): no others are built.
+int launch_big2(const ConvPlan &p, const ConvArgs &a, const float *afrag, dim3 grid, hipStream_t st) {
+  const unsigned xb = p.buf ? (unsigned)p.xbytes : 0u, ab = p.buf ? (unsigned)p.abytes : 0u;
+#define AP_BIG2(BM_, BN_, BUF_, P1_) \
+  case BM_ * 1000 + BN_ * 4 + BUF_ * 2 + P1_: conv2d_f32_big2_kernel<BM_, BN_, BUF_, P1_><<<grid, 256, 0, st>>>(a, afrag, xb, ab); return 0;
+  switch (p.BM * 1000 + p.BN * 4 + p.buf * 2 + p.p1) {
+    AP_BIG2(128, 128, true, true) AP_BIG2(128, 128, true, false) AP_BIG2(128, 128, false, false)
+    AP_BIG2(128, 64, true, true) AP_BIG2(128, 64, true, false) AP_BIG2(128, 64, false, false)
+    AP_BIG2(64, 128, true, false) AP_BIG2(64, 128, false, false)
+    AP_BIG2(64, 64, true, false) AP_BIG2(64, 64, false, false)
+#ifdef AP_TOOLS
+    AP_BIG2(64, 128, true, true) AP_BIG2(64, 64, true, true)
+#endif
+  }
+#undef AP_BIG2
+  set_error("ap_conv2d_fwd: no streamed-weight kernel %d x %d buf %d p1 %d", p.BM, p.BN, (int)p.buf, (int)p.p1); return -22;
+}
+void launch_split(const ConvPlan &p, const ConvArgs &a, const float *wT, const ConvImages &im, dim3 grid, hipStream_t st) {
+  if (p.family == CONV_SPLITH && p.BM == 128) conv2d_split_kernel<128, 128, true><<<grid, 256, 0, st>>>(a, wT + im.splith);
+  else if (p.family == CONV_SPLITH) conv2d_split_kernel<64, 128, true><<<grid, 256, 0, st>>>(a, wT + im.splith);
+  else if (p.BM == 128) conv2d_split_kernel<128, 128><<<grid, 256, 0, st>>>(a, wT + im.split);
+  else conv2d_split_kernel<64, 128><<<grid, 256, 0, st>>>(a, wT + im.split);
+}
+void launch_few(const ConvPlan &p, const ConvArgs &a, dim3 grid, hipStream_t st) {
+#define AP_FEW(MO_, K3_) case (K3_ ? -MO_ : MO_): conv2d_few_kernel<MO_, K3_><<<grid, 256, p.lds, st>>>(a); break;
+  switch (p.k3_nb ? -p.BM : p.BM) { AP_FEW(1, true) AP_FEW(2, true) AP_FEW(3, true) AP_FEW(4, true) AP_FEW(1, false) AP_FEW(2, false) AP_FEW(3, false) AP_FEW(4, false) }
+#undef AP_FEW
+}
+// launches what the plan says (p.family / p.cls are rewritten where the tools build's pointwise kernel took the layer instead)
+int conv_launch(ConvPlan &p, const ConvArgs &a, const ConvImages &im, hipStream_t st) {
+  const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+  const bool raw = p.splits > 1;                    // K slices write raw partial sums: bias / residual / ReLU move to the reduce
+#ifdef AP_TOOLS
+  if (p.try_p1 && conv_p1_serves(a.B, a.Cin, a.H, a.W, a.Cout, a.kh, a.kw, a.stride, a.pad, a.groups)) {
+    const int rc = launch_conv_p1(a.x, a.wT + im.frag, a.bias, a.res, a.out, a.B, a.Cin, a.H, a.W, a.Cout, a.relu, a.x_cstride, a.x_coff,
+                                  a.o_cstride, a.o_coff, p.abytes, st);
+    if (rc != 1) { p.family = CONV_P1; p.cls = conv_class(CONV_P1, 0, 0); return rc; }
+  }
+#endif
+  int rc = 0;
+  switch (p.family) {
+    case CONV_W3:
+      rc = launch_conv_w3(a.x, a.wT + im.w3, raw ? nullptr : a.bias, raw ? nullptr : a.res, a.out, a.B, a.Cin, a.H, a.W, a.Cout,
+                          raw ? 0 : a.relu, a.x_cstride, a.x_coff, a.o_cstride, a.o_coff, st, p.splits, a.part); break;
+    case CONV_BIG2: rc = launch_big2(p, a, a.wT + im.frag, grid, st); break;
+    case CONV_SPLIT: case CONV_SPLITH: launch_split(p, a, a.wT, im, grid, st); break;
+    case CONV_FEW: launch_few(p, a, grid, st); break;
+    case CONV_BIG: conv2d_f32_big_kernel<<<grid, 256, 0, st>>>(a); break;
+    default: conv2d_f32_kernel<<<grid, 256, 0, st>>>(a); break;
+  }
+  if (rc) return rc;
+  if (p.reduce) {                                   // the slices summed in order (deterministic), + bias / residual / ReLU
+    const size_t total = (size_t)a.B * a.Cout * a.Ho * a.Wo;
+    conv_splitk_reduce_kernel<<<(unsigned)((total / 4 + 255) / 256 + 1), 256, 0, st>>>(a, total);
+  }
+  AP_HIP(hipGetLastError());
+  return 0;
+}
+int conv2d_fwd_impl(const float *x, const float *wT, const float *bias, const float *res, float *out, int B, int Cin, int H,
+                    int W, int Cout, int kh, int kw, int stride, int pad, int groups, int flags, int x_cstride, int x_coff,
+                    void *stream, int o_cstride, int o_coff, ConvGeom *g, int *cls) {
+  if (!x || !wT || !out || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0 ||
+      groups < 1 || Cin % groups || Cout % groups || x_cstride < x_coff + Cin) { set_error("ap_conv2d_fwd: bad argument"); return -22; }
+  *g = conv_geom(B, Cin, H, W, Cout, kh, kw, stride, pad, groups, flags, x_cstride, o_cstride, o_coff);
+  const ConvImages im = conv_images(Cout, Cin / groups, kh, kw, groups);
+  const ConvWs ws = conv_ws_here();
+  ConvPlan p;
+  if (const int rc = conv_plan(*g, im, g_conv_tune, ws.p ? ws.bytes : 0, &p)) { set_error("%s", p.err); return rc; }
+  ConvArgs a;
+  a.x = x; a.wT = wT; a.bias = bias; a.res = res; a.out = out;
+  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.Ho = g->Ho; a.Wo = g->Wo; a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
+  a.groups = groups; a.relu = g->relu; a.pad_h = g->pad_h; a.dil_h = g->dil_h; a.dil_w = g->dil_w;
+  a.x_cstride = x_cstride; a.x_coff = x_coff; a.o_cstride = g->o_cstride; a.o_coff = g->o_coff;
+  a.splits = p.splits; a.part = p.splits > 1 ? ws.p : nullptr;
+  const int rc = conv_launch(p, a, im, (hipStream_t)stream);
+  *cls = p.cls;
+  return rc;
+}
+}  // namespace
+
 static int conv2d_fwd_entry(const float *x, const float *wT, const float *bias, const float *res, float *out, int B,
-                            int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups, int relu,
+                            int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups, int flags,
                             int x_cstride, int x_coff, void *stream, int o_cstride, int o_coff) {
+  ConvGeom g;
   int cls = 5;
-  if (!g_cprof.on)
-    return conv2d_fwd_impl(x, wT, bias, res, out, B, Cin, H, W, Cout, kh, kw, stride, pad, groups, relu, x_cstride, x_coff, stream, &cls,
-                           o_cstride, o_coff);
-  if (g_cprof.used + 2 > g_cprof.ev.size())
-    for (int i = 0; i < 2; i++) {
-      hipEvent_t e;
-      AP_HIP(hipEventCreate(&e));
-      g_cprof.ev.push_back(e);
-    }
-  AP_HIP(hipEventRecord(g_cprof.ev[g_cprof.used], (hipStream_t)stream));
-  const int rc = conv2d_fwd_impl(x, wT, bias, res, out, B, Cin, H, W, Cout, kh, kw, stride, pad, groups, relu, x_cstride, x_coff, stream, &cls,
-                                 o_cstride, o_coff);
+  const bool prof = g_cprof.on;
+  while (prof && g_cprof.used + 2 > g_cprof.ev.size()) {
+    hipEvent_t e;
+    AP_HIP(hipEventCreate(&e));
+    g_cprof.ev.push_back(e);
+  }
+  if (prof) AP_HIP(hipEventRecord(g_cprof.ev[g_cprof.used], (hipStream_t)stream));
+  const int rc = conv2d_fwd_impl(x, wT, bias, res, out, B, Cin, H, W, Cout, kh, kw, stride, pad, groups, flags, x_cstride, x_coff, stream,
+                                 o_cstride, o_coff, &g, &cls);
+  if (!prof) return rc;
   AP_HIP(hipEventRecord(g_cprof.ev[g_cprof.used + 1], (hipStream_t)stream));
   if (rc) return rc;
-  const bool one_d = (relu >> 9) & 1;
-  const int dil = (relu >> 16) ? (relu >> 16) : 1;
-  const int ph = one_d ? 0 : pad, dh = one_d ? 1 : dil;
-  const long long Ho = (H + 2 * ph - dh * (kh - 1) - 1) / stride + 1, Wo = (W + 2 * pad - dil * (kw - 1) - 1) / stride + 1;
   g_cprof.used += 2;
-  g_cprof.flop.push_back(2.0 * (double)B * Ho * Wo * Cout * (double)(Cin / groups) * kh * kw);
+  g_cprof.flop.push_back(2.0 * (double)g.N * Cout * (double)(Cin / groups) * kh * kw);
   g_cprof.cls.push_back(cls);
   for (int v : {B, Cin, H, W, Cout, kh, kw, stride, groups}) g_cprof.shape.push_back(v);
   return 0;
 }
 
 // the same convolution with `out` a channel slice [out_coff, out_coff + Cout) of a tensor of out_cstride channels (torch.cat's
-// destination: the producer writes its half in place).  Served by the streamed-weight fp32 kernel (and its split-K reduce) only.
+// destination: the producer writes its half in place).  For layers the streamed-weight fp32 kernel serves: that kernel, its split-K
+// reduce, or the F(2,3) kernel where conv_plan prefers it.
 extern "C" int ap_conv2d_fwd_slice(const float *x, const float *wT, const float *bias, const float *res, float *out, int B,
                                    int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups, int relu,
                                    int x_cstride, int x_coff, int out_cstride, int out_coff, void *stream) {
@@ -1189,199 +1183,6 @@ extern "C" int ap_conv2d_fwd(const float *x, const float *wT, const float *bias,
                              int x_cstride, int x_coff, void *stream) {
   return conv2d_fwd_entry(x, wT, bias, res, out, B, Cin, H, W, Cout, kh, kw, stride, pad, groups, relu, x_cstride, x_coff, stream, 0, 0);
 }
-
-namespace {
-int conv2d_fwd_impl(const float *x, const float *wT, const float *bias, const float *res, float *out, int B, int Cin, int H,
-                    int W, int Cout, int kh, int kw, int stride, int pad, int groups, int relu, int x_cstride, int x_coff,
-                    void *stream, int *cls, int o_cstride, int o_coff) {
-  if (!x || !wT || !out || B < 1 || Cin < 1 || Cout < 1 || H < 1 || W < 1 || kh < 1 || kw < 1 || stride < 1 || pad < 0 ||
-      groups < 1 || Cin % groups || Cout % groups || x_cstride < x_coff + Cin) {
-    set_error("ap_conv2d_fwd: bad argument");
-    return -22;
-  }
-  ConvArgs a;
-  a.x = x; a.wT = wT; a.bias = bias; a.res = res; a.out = out;
-  a.B = B; a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
-  // flags: bit 0 ReLU, bit 8 AP_CONV_SPLIT, bit 10 AP_CONV_SPLIT_F16, bit 9 AP_CONV_1D (padding and dilation apply to W only: Conv1d over
-  // [B][C][1][L]), bits 16-31 dilation (0 = 1)
-  const bool split = (relu >> 8) & 1, one_d = (relu >> 9) & 1, splith = (relu >> 10) & 1;
-  const int dil = (relu >> 16) ? (relu >> 16) : 1;
-  relu &= 1;
-  a.groups = groups; a.relu = relu; a.x_cstride = x_cstride; a.x_coff = x_coff;
-  a.splits = 1; a.part = nullptr;
-  a.o_cstride = o_cstride ? o_cstride : Cout; a.o_coff = o_cstride ? o_coff : 0;
-  const bool sliced = a.o_cstride != Cout || a.o_coff != 0;
-  a.dil_w = dil;
-  a.dil_h = one_d ? 1 : dil;
-  a.pad_h = one_d ? 0 : pad;
-  a.Ho = (H + 2 * a.pad_h - a.dil_h * (kh - 1) - 1) / stride + 1;
-  a.Wo = (W + 2 * pad - a.dil_w * (kw - 1) - 1) / stride + 1;
-  if (a.Ho < 1 || a.Wo < 1) { set_error("ap_conv2d_fwd: empty output"); return -22; }
-  const long long N = (long long)B * a.Ho * a.Wo;
-  const int Mg = Cout / groups;
-  // the 128 x 128 tile needs enough workgroups to fill 256 CUs; otherwise 4x as many 64 x 64 tiles win
-  const long long tiles128 = ((N + 127) / 128) * ((Mg + 127) / 128) * (long long)groups;
-  const bool many = tiles128 >= 512;
-  if (sliced && !(conv_has_frag(Cout, Cin / groups, groups) && !g_conv_no_frag && !split && !splith)) {
-    set_error("ap_conv2d_fwd_slice: this layer is not served by the streamed-weight fp32 kernel (Cin/g %% 16, Cout/g >= 64, no split-operand flag)");
-    return -22;
-  }
-  if (g_conv_w3 && !split && !splith && !one_d && dil == 1 && conv_w3_serves(Cin, H, W, Cout, kh, kw, stride, pad, groups) &&
-      (size_t)B * x_cstride * H * W * sizeof(float) < ((size_t)1 << 31) && (size_t)B * a.o_cstride * H * W * sizeof(float) < ((size_t)1 << 31) &&
-      (long long)B * H * (W / 2) >= g_conv_w3_min_pairs) {
-    const float *wimg = wT + conv_w3_offset(Cout, Cin, kh, kw, groups);
-    if (g_conv_w3 == 2 || conv_w3_worth(B, H, W, Cout)) {       // (g_conv_w3 == 2, tools: every served layer, unsliced)
-      *cls = 6;
-      return launch_conv_w3(x, wimg, bias, res, out, B, Cin, H, W, Cout, relu, x_cstride, x_coff, a.o_cstride, a.o_coff, (hipStream_t)stream);
-    }
-    // too few tiles for one workgroup per CU (the UNet's 8 x 8 and 4 x 4 maps): K slices into the caller's workspace, summed in
-    // order by the reduce kernel (which also adds bias / residual / ReLU) -- deterministic
-    const ConvWs cws = g_conv_w3_split ? conv_ws_here() : ConvWs{};
-    const int S = cws.p ? conv_w3_splits(B, Cin, H, W, Cout, cws.bytes) : 0;
-    if (S > 1) {
-      *cls = 6;
-      int rc = launch_conv_w3(x, wimg, nullptr, nullptr, out, B, Cin, H, W, Cout, 0, x_cstride, x_coff, a.o_cstride, a.o_coff, (hipStream_t)stream, S, cws.p);
-      if (rc) return rc;
-      a.splits = S;
-      a.part = cws.p;
-      const size_t total = (size_t)B * Cout * a.Ho * a.Wo;
-      conv_splitk_reduce_kernel<<<(unsigned)((total / 4 + 255) / 256 + 1), 256, 0, (hipStream_t)stream>>>(a, total);
-      AP_HIP(hipGetLastError());
-      return 0;
-    }
-  }
-  if (conv_has_frag(Cout, Cin / groups, groups) && !g_conv_no_frag) {
-    const size_t n1 = (size_t)Cout * (Cin / groups) * kh * kw;
-    const float *afrag = wT + ((n1 + 3) & ~(size_t)3);
-    // buffer-load form of the fp32 kernel: the activations' slab and the fragment image each below 2 GB (32-bit offsets,
-    // bit 31 marks the padding taps); larger tensors keep the pointer form
-    const size_t xbytes = (size_t)B * x_cstride * H * W * sizeof(float);
-    const size_t abytes = conv_frag_elems(Cout, Cin / groups, kh, kw, groups) * sizeof(float);
-    const bool buf = xbytes < ((size_t)1 << 31) && abytes < ((size_t)1 << 31);
-    const bool p1 = kh == 1 && kw == 1 && stride == 1 && pad == 0 && !one_d && (H * W) % 4 == 0;   // pointwise: 16-byte staging
-#ifdef AP_TOOLS
-    if (g_conv_p1 && p1 && buf && !split && !splith && conv_p1_serves(B, Cin, H, W, Cout, kh, kw, stride, pad, groups)) {
-      const int rc = launch_conv_p1(x, afrag, bias, res, out, B, Cin, H, W, Cout, relu, x_cstride, x_coff, a.o_cstride, a.o_coff, abytes,
-                                    (hipStream_t)stream);
-      if (rc != 1) {
-        *cls = 7;
-        return rc;
-      }
-    }
-#endif
-    if (splith) {                                               // two fp16 parts per operand, three partial products
-      const void *hfrag = afrag + conv_frag_elems(Cout, Cin / groups, kh, kw, groups) +
-                          conv_split_floats(Cout, Cin / groups, kh, kw, groups);
-      if (Mg < 128) {
-        dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 63) / 64), (unsigned)groups);
-        *cls = 3;
-        conv2d_split_kernel<64, 128, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, hfrag);
-      } else {
-        dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 127) / 128), (unsigned)groups);
-        *cls = 3;
-        conv2d_split_kernel<128, 128, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, hfrag);
-      }
-    } else if (split) {                                         // fp32 results on the bf16 pipe (3-way split operands)
-      const __bf16 *sfrag = reinterpret_cast<const __bf16 *>(afrag + conv_frag_elems(Cout, Cin / groups, kh, kw, groups));
-      if (Mg < 128) {
-        dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 63) / 64), (unsigned)groups);
-        *cls = 3;
-        conv2d_split_kernel<64, 128><<<grid, 256, 0, (hipStream_t)stream>>>(a, sfrag);
-      } else {
-        dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 127) / 128), (unsigned)groups);
-        *cls = 3;
-        conv2d_split_kernel<128, 128><<<grid, 256, 0, (hipStream_t)stream>>>(a, sfrag);
-      }
-#ifdef AP_TOOLS
-    } else if (g_conv_force && buf && groups == 1) {                   // tools: one tile shape for every layer (sweeps)
-      const int fm = (g_conv_force == 4 || g_conv_force == 5) ? 128 : 64, fn = (g_conv_force == 4 || g_conv_force == 7) ? 128 : 64;
-      dim3 grid((unsigned)((N + fn - 1) / fn), (unsigned)((Mg + fm - 1) / fm), 1u);
-      *cls = 2;
-#define AP_FORCE(BM_, BN_)                                                                                                          \
-  do {                                                                                                                              \
-    if (p1) conv2d_f32_big2_kernel<BM_, BN_, true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes); \
-    else conv2d_f32_big2_kernel<BM_, BN_, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);          \
-  } while (0)
-      if (g_conv_force == 4) AP_FORCE(128, 128);
-      else if (g_conv_force == 5) AP_FORCE(128, 64);
-      else if (g_conv_force == 6) AP_FORCE(64, 64);
-      else AP_FORCE(64, 128);
-#undef AP_FORCE
-#endif
-    } else if (Mg < 128) {                                             // 64 <= Cout/g < 128
-      dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 63) / 64), (unsigned)groups);
-      *cls = 1;
-      if (buf) conv2d_f32_big2_kernel<64, 128, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else conv2d_f32_big2_kernel<64, 128, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, 0u, 0u);
-    } else if (tiles128 >= g_conv_frag_min_tiles && !(kh == 1 && kw == 1 && !g_conv_wide_1x1)) {   // (pointwise layers: 128 x 64 below)
-      dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 127) / 128), (unsigned)groups);
-      *cls = 0;
-      if (buf && p1) conv2d_f32_big2_kernel<128, 128, true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else if (buf) conv2d_f32_big2_kernel<128, 128, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else conv2d_f32_big2_kernel<128, 128, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, 0u, 0u);
-    } else if (const ConvWs cws = (buf && groups == 1 && !split && !splith && tiles128 * 2 < g_conv_splitk_t2 && kh * kw * (Cin / 16) >= 32)
-                                      ? conv_ws_here() : ConvWs{};
-               cws.p && 2 * (size_t)B * Cout * a.Ho * a.Wo * sizeof(float) <= cws.bytes) {
-      // too few output tiles for 256 CUs and a long K (the 4 x 4 and 8 x 8 maps of the UNet: K = 2 304 .. 4 608): split-K over
-      // blockIdx.z, partial sums to the caller's workspace, slices summed in order by a second small kernel (deterministic)
-      const long long t64 = ((N + 63) / 64) * ((Mg + 63) / 64), t128x64 = ((N + 63) / 64) * ((Mg + 127) / 128);
-      const bool small = t128x64 < 192;
-      const long long tiles = small ? t64 : t128x64;
-      int S = 2;
-      while (S < 8 && tiles * S < g_conv_splitk_cap && kh * kw * (Cin / 16) / (2 * S) >= 16 &&
-             (size_t)(2 * S) * B * Cout * a.Ho * a.Wo * sizeof(float) <= cws.bytes) S *= 2;
-      a.splits = S;
-      a.part = cws.p;
-      *cls = 2;
-      if (small) {
-        dim3 grid((unsigned)((N + 63) / 64), (unsigned)((Mg + 63) / 64), (unsigned)S);
-        conv2d_f32_big2_kernel<64, 64, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      } else {
-        dim3 grid((unsigned)((N + 63) / 64), (unsigned)((Mg + 127) / 128), (unsigned)S);
-        conv2d_f32_big2_kernel<128, 64, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      }
-      const size_t total = (size_t)B * Cout * a.Ho * a.Wo;
-      conv_splitk_reduce_kernel<<<(unsigned)((total / 4 + 255) / 256 + 1), 256, 0, (hipStream_t)stream>>>(a, total);
-    } else if (((N + 63) / 64) * ((Mg + 127) / 128) * (long long)groups >= 192) {   // few tiles (low-resolution layers): 128 x 64
-      dim3 grid((unsigned)((N + 63) / 64), (unsigned)((Mg + 127) / 128), (unsigned)groups);
-      *cls = 2;
-      if (buf && p1) conv2d_f32_big2_kernel<128, 64, true, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else if (buf) conv2d_f32_big2_kernel<128, 64, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else conv2d_f32_big2_kernel<128, 64, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, 0u, 0u);
-    } else {                                                    // fewer still (4 x 4 maps, the embedding's linear layers): 64 x 64,
-      dim3 grid((unsigned)((N + 63) / 64), (unsigned)((Mg + 63) / 64), (unsigned)groups);   // twice the workgroups for 256 CUs
-      *cls = 2;
-      if (buf) conv2d_f32_big2_kernel<64, 64, true><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, (unsigned)xbytes, (unsigned)abytes);
-      else conv2d_f32_big2_kernel<64, 64, false><<<grid, 256, 0, (hipStream_t)stream>>>(a, afrag, 0u, 0u);
-    }
-  } else if (groups == 1 && Cout <= 4 && (size_t)Cin * kh * kw * Cout * sizeof(float) <= 48 * 1024) {
-    const unsigned grid = (unsigned)((N + 255) / 256);
-    const size_t sh = (size_t)Cin * kh * kw * Cout * sizeof(float);
-    *cls = 5;
-    const bool k3 = kh == 3 && kw == 3 && a.dil_h == 1 && a.dil_w == 1;
-    switch (k3 ? -Cout : Cout) {
-      case -1: conv2d_few_kernel<1, true><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case -2: conv2d_few_kernel<2, true><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case -3: conv2d_few_kernel<3, true><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case -4: conv2d_few_kernel<4, true><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case 1: conv2d_few_kernel<1><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case 2: conv2d_few_kernel<2><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      case 3: conv2d_few_kernel<3><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-      default: conv2d_few_kernel<4><<<grid, 256, sh, (hipStream_t)stream>>>(a); break;
-    }
-  } else if (Mg >= 128 && kh <= 3 && kw <= 3 && many) {
-    dim3 grid((unsigned)((N + 127) / 128), (unsigned)((Mg + 127) / 128), (unsigned)groups);
-    *cls = 4;
-    conv2d_f32_big_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  } else {
-    dim3 grid((unsigned)((N + CBN - 1) / CBN), (unsigned)((Mg + CBM - 1) / CBM), (unsigned)groups);
-    *cls = 5;
-    conv2d_f32_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(a);
-  }
-  AP_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace
 
 extern "C" int ap_affine_nchw(const float *x, const float *scale, const float *shift, float *y, int B, int C, int HW,
                               int x_cstride, int x_coff, int relu, void *stream) {
@@ -1737,7 +1538,7 @@ extern "C" int ap_groupnorm_nchw(const float *x, const float *gamma, const float
   if (!x || !gamma || !beta || !y || B < 1 || C < 1 || HW < 1 || groups < 1 || C % groups) { set_error("ap_groupnorm_nchw: bad argument"); return -22; }
   hipStream_t st = (hipStream_t)stream;
   const int slabs = B * groups, n = (C / groups) * HW, n4 = n / 4;
-  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && !g_conv_no_frag;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && !g_conv_tune.no_frag;
 #define AP_GN(T, NV)                                                                                                          \
   groupnorm_reg_kernel<T, NV><<<(unsigned)((slabs + 256 / T - 1) / (256 / T)), 256, 0, st>>>(x, gamma, beta, scale_shift, y, C, HW, \
                                                                                             groups, eps, act, slabs)
@@ -1786,7 +1587,7 @@ extern "C" int ap_attention_qkv(const float *qkv, float *out, int B, int C, int 
   const float scale2 = 1.0f / sqrtf((float)ch);          // (1/sqrt(sqrt(ch)))^2, unet.py:247-249
   hipStream_t st = (hipStream_t)stream;
   const unsigned grid = (unsigned)(B * heads);
-  if (ch == 64 && (T == 64 || T == 256) && !g_conv_no_frag) {   // the UNet's shapes: fp32 MFMA
+  if (ch == 64 && (T == 64 || T == 256) && !g_conv_tune.no_frag) {   // the UNet's shapes: fp32 MFMA
     const size_t sm2 = (size_t)(64 * T + T * 65) * sizeof(float);
     static bool attr2 = false;
     if (!attr2) {

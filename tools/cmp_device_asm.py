@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
 """Is the device code of two source trees the same?  No GPU needed.
 
-    python tools/cmp_device_asm.py <tree A> <tree B> [source.hip ...]
+    python tools/cmp_device_asm.py [--by-symbol] <tree A> <tree B> [source.hip ...]
 
 Compiles every source of HIP_SOURCES (product flags) and of HIP_SOURCES + TOOLS_ONLY_SOURCES (-DAP_TOOLS) of both trees to gfx950
 assembly with the flags build_hip gives that file plus `--cuda-device-only -S`, and compares the two outputs line by line.  Dropped
 before comparing: comment lines, `.file` / `.ident` lines and the `__hip_cuid_<hash>` symbol (a hash of the source text).
 Prints identical/different per file and exits 1 if any file differs -- the check of a refactor that must not move an instruction.
+--by-symbol: a file that differs line by line still counts as identical if its symbols are the same set and every symbol's text
+(function, kernel descriptor, metadata entry; the function's running number taken out of local labels) is the same -- a reordered
+host launcher changes the order in which template instantiations are emitted and nothing else.
 """
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -36,18 +40,49 @@ def device_asm(tree, name, tools):
     return keep
 
 
+_ANNOUNCE = re.compile(r"^\s*(?:\.(?:globl|weak|protected|hidden)\s+([^\s,]+)|\.section\s+\.text\.([^\s,]+),)")
+_LOCAL = re.compile(r"(\.L|Header=)(BB|func_begin|func_end|tmp)\d+")
+
+
+def by_symbol(lines):
+    """{symbol: its lines}: function text + kernel descriptor (from the first directive that names the symbol to the next symbol's)
+    and, under "meta:<symbol>", its entry of the metadata's kernel list; "" holds what belongs to no symbol.  The per-function
+    number in local labels (.LBB<n>_<k>, .Lfunc_end<n>) is dropped: it is the function's position in the file."""
+    out, key, meta = {}, "", False
+    for line in lines:
+        if ".amdgpu_metadata" in line:
+            meta, key = not line.strip().startswith(".end"), ""
+        if meta and line.startswith("  - "):
+            key = ("meta", len(out))                    # named by the entry's own .name line below
+        elif not meta:
+            m = _ANNOUNCE.match(line)
+            if m:
+                key = m.group(1) or m.group(2)
+        if meta and isinstance(key, tuple) and line.startswith("    .name:"):
+            out["meta:" + line.split()[1]] = out.pop(key)
+            key = "meta:" + line.split()[1]
+        out.setdefault(key, []).append(_LOCAL.sub(r"\1\2", line))
+    return out
+
+
 def main():
-    a, b = (os.path.abspath(p) for p in sys.argv[1:3])
+    args = [x for x in sys.argv[1:] if x != "--by-symbol"]
+    sym = "--by-symbol" in sys.argv[1:]
+    a, b = (os.path.abspath(p) for p in args[:2])
     jobs = [(n, False) for n in G.HIP_SOURCES] + [(n, True) for n in G.HIP_SOURCES + G.TOOLS_ONLY_SOURCES]
-    if sys.argv[3:]:
-        jobs = [j for j in jobs if j[0] in sys.argv[3:]]
+    if args[2:]:
+        jobs = [j for j in jobs if j[0] in args[2:]]
     with ThreadPoolExecutor(int(os.environ.get("MAX_JOBS", "8"))) as ex:
         res = list(ex.map(lambda j: (device_asm(a, *j), device_asm(b, *j)), jobs))
     bad = 0
     for (name, tools), (xa, xb) in zip(jobs, res):
-        same = xa == xb
+        same, note = xa == xb, ""
+        if not same and sym:                            # the same symbols with the same text, emitted in another order
+            sa, sb = by_symbol(xa), by_symbol(xb)
+            diff = sorted(k for k in set(sa) | set(sb) if sa.get(k) != sb.get(k))
+            same, note = not diff, f"  ({len(sa)} symbols, order differs)" if not diff else "  differing symbols: " + " ".join(map(str, diff[:6]))
         bad += not same
-        print(f"{'tools  ' if tools else 'product'} {name:28s} {len(xa):7d} lines  {'identical' if same else 'DIFFERENT'}")
+        print(f"{'tools  ' if tools else 'product'} {name:28s} {len(xa):7d} lines  {'identical' if same else 'DIFFERENT'}{note}")
     print(f"{len(jobs) - bad} of {len(jobs)} identical")
     return 1 if bad else 0
 
