@@ -112,6 +112,7 @@ extern "C" int ap_ctx_create(const ap_config *cfg, ap_ctx **out) {
   c->profile = false;
   c->ev_used = 0;
   c->skip_group = 0;
+  c->n_cu = 256; c->drop_B = 0;
   const int T = cfg->T;
   // calc_diffusion_hyperparams (util.py:96-123), closed form in double rounded to fp32
   c->Beta.resize(T); c->Alpha.resize(T); c->Alpha_bar.resize(T); c->Sigma.resize(T);
@@ -209,6 +210,7 @@ extern "C" int ap_ctx_set_f32_form(ap_ctx *ctx, int form) {
     return -22;
   }
   ctx->f32_form = form;
+  forget_plans(ctx);
   return 0;
 }
 
@@ -288,6 +290,8 @@ extern "C" int ap_ctx_load_wavenet(ap_ctx *ctx, const float *blob_dev, size_t n_
   AP_HIP(hipMemcpyAsync(ctx->emb_freq, embed_freq_dev, sizeof(float) * (Ein / 2), hipMemcpyDeviceToDevice, st));
   int rc = launch_fold_and_pack(ctx, blob_dev, st);
   if (rc) return rc;
+  ctx->n_cu = device_cu_count();                                // (the context lives on the device its weights are loaded on)
+  forget_plans(ctx);
   ctx->bwd_ready = false;                                       // (re-loaded weights: the backward images are rebuilt by the next ap_ctx_prepare_backward)
   if (c.precision == AP_PREC_BF16 || c.precision == AP_PREC_BF16_STORE) {
     const size_t n1 = NL * 2 * C * C * 3, n2 = NL * (C + S) * C;
@@ -411,79 +415,39 @@ int check_run(ap_ctx *ctx, int B, int L, void *ws, size_t ws_bytes, const char *
   return 0;
 }
 
-// the 36-layer sweep: h ping-pongs between ha/hb, skip accumulates (WaveNet.py:120-135,164-170)
-// one AP_PREC_BF16_STORE block launch (its own pair of profile events: kind 0)
-int launch_resblock_u_timed(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st,
-                            void *fout = nullptr) {
-  ProfileSpan span;
-  if (int e = span.begin(ctx, 0, st)) return e;
-  const int rc = launch_resblock_bf16u(ctx, layer, uin, pt_next, uout, gout, B, L, st, fout);
-  if (int e = span.end()) return e;
-  return rc;
-}
-
-// one skip GEMM (its own pair of profile events: kind 1)
-int skip_gemm_timed(ap_ctx *ctx, int n0, int nl, const Ws &w, int B, int L, hipStream_t st) {
-  ProfileSpan span;
-  if (int e = span.begin(ctx, 1, st)) return e;
-  const int rc = launch_skipgemm_bf16(ctx, n0, nl, w.gimg, w.skip, n0 > 0, B, L, st);
-  if (int e = span.end()) return e;
-  return rc;
-}
-
-// AP_PREC_BF16_STORE: the sweep over bf16 u images (ap_resblock_bf16u.hip), skip through the deferred-skip GEMM
-int run_net_bstore(ap_ctx *ctx, const float *x, const Ws &w, int B, int L, hipStream_t st) {
-  int rc = launch_init_conv_u(ctx, x, w.pt, w.ha, B, L, st);
-  if (rc) return rc;
-  void *uin = w.ha, *uout = w.hb;
-  const int G = skip_group_of(ctx);
-  for (int n0 = 0; n0 < ctx->NL; n0 += G) {
-    const int nl = ctx->NL - n0 < G ? ctx->NL - n0 : G;
-    for (int n = n0; n < n0 + nl; n++) {
-      const bool last = n + 1 == ctx->NL;
-      rc = launch_resblock_u_timed(ctx, n, uin, last ? nullptr : w.pt + (size_t)(n + 1) * ctx->C, last ? nullptr : uout,
-                                   w.gimg + (size_t)(n - n0) * w.gslot, B, L, st);
-      if (rc) return rc;
-      void *t = uin; uin = uout; uout = t;
-    }
-    rc = skip_gemm_timed(ctx, n0, nl, w, B, L, st);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
+// the sweep over the layers: h (AP_PREC_BF16_STORE: the bf16 u image) ping-pongs between ha / hb (WaveNet.py:120-135,164-170).  A group is
+// G layers and, in the deferred-skip form (AP_PREC_BF16 with a skip group, AP_PREC_BF16_STORE), one GEMM that adds their skip_conv outputs
+// from the bf16 g images into skip (a plain store for the first group); the fused form is one group of all layers without a GEMM.
 int run_net(ap_ctx *ctx, const float *x, float step, const Ws &w, int B, int L, hipStream_t st) {
   int rc = launch_embed(ctx, step, w.pt, st);
   if (rc) return rc;
-  if (ctx->cfg.precision == AP_PREC_BF16_STORE) return run_net_bstore(ctx, x, w, B, L, st);
-  rc = launch_init_conv(ctx, x, w.ha, B, L, st);
+  const bool u = ctx->cfg.precision == AP_PREC_BF16_STORE, defer = w.gimg != nullptr;
+  rc = u ? launch_init_conv_u(ctx, x, w.pt, w.ha, B, L, st) : launch_init_conv(ctx, x, w.ha, B, L, st);
   if (rc) return rc;
-  float *hin = w.ha, *hout = w.hb;
-  if (w.gimg) {
-    // deferred-skip form (AP_PREC_BF16): every block writes h' and its bf16 g image; after each group of G layers one GEMM adds
-    // the group's skip_conv outputs into skip (a plain store for the first group)
-    const int G = ctx->skip_group;
-    for (int n0 = 0; n0 < ctx->NL; n0 += G) {
-      const int nl = ctx->NL - n0 < G ? ctx->NL - n0 : G;
-      for (int n = n0; n < n0 + nl; n++) {
-        // (the last layer's h' is never read -- WaveNet.py:131-135 returns the skip sum only: null = leave res_conv and its store out)
-        rc = launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, n + 1 == ctx->NL ? nullptr : hout, nullptr, 0, B, L, st, nullptr,
-                             w.gimg + (size_t)(n - n0) * w.gslot);
-        if (rc) return rc;
-        float *t = hin; hin = hout; hout = t;
-      }
-      rc = skip_gemm_timed(ctx, n0, nl, w, B, L, st);
-      if (rc) return rc;
-    }
-    return 0;
+  // (the last layer's h' is never read, WaveNet.py:131-135: null = leave res_conv and its store out, where the launch has such a form)
+  if (!g_keep_plans || ctx->drop_B != B || ctx->drop_L != L || ctx->drop_defer != (int)defer) {   // (once per shape, not once per call)
+    ctx->drop_last = block_drops_last_h(block_ask(ctx, 0, B, L, false, !defer, false, defer, false, u), g_block_tune);
+    ctx->drop_B = B; ctx->drop_L = L; ctx->drop_defer = defer;
   }
-  // (the last layer's h' is never read -- WaveNet.py:131-135 returns the skip sum only; the minimal-filtering block leaves
-  // res_conv and its store out when handed a null h')
-  const bool drop_last = resblock_f32w_serves(ctx, B, L);
-  for (int n = 0; n < ctx->NL; n++) {
-    rc = launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, (drop_last && n + 1 == ctx->NL) ? nullptr : hout, w.skip, n > 0, B, L, st);
+  const bool drop_last = ctx->drop_last;
+  float *hin = w.ha, *hout = w.hb;
+  const int G = defer ? skip_group_of(ctx) : ctx->NL;
+  for (int n0 = 0; n0 < ctx->NL; n0 += G) {
+    const int nl = ctx->NL - n0 < G ? ctx->NL - n0 : G;
+    for (int n = n0; n < n0 + nl; n++) {
+      float *ho = (drop_last && n + 1 == ctx->NL) ? nullptr : hout;
+      char *g = defer ? w.gimg + (size_t)(n - n0) * w.gslot : nullptr;
+      rc = u ? launch_resblock_bf16u(ctx, n, hin, ho ? w.pt + (size_t)(n + 1) * ctx->C : nullptr, ho, g, B, L, st)
+             : launch_resblock(ctx, n, hin, w.pt + (size_t)n * ctx->C, ho, defer ? nullptr : w.skip, defer ? 0 : n > 0, B, L, st, nullptr, g);
+      if (rc) return rc;
+      float *t = hin; hin = hout; hout = t;
+    }
+    if (!defer) continue;
+    ProfileSpan span;                                            // the group's skip GEMM: its own pair of profile events, kind 1
+    if (int e = span.begin(ctx, 1, st)) return e;
+    rc = launch_skipgemm_bf16(ctx, n0, nl, w.gimg, w.skip, n0 > 0, B, L, st);
+    if (int e = span.end()) return e;
     if (rc) return rc;
-    float *t = hin; hin = hout; hout = t;
   }
   return 0;
 }
@@ -506,7 +470,7 @@ extern "C" int ap_init_conv(ap_ctx *ctx, const float *x, float *h, int B, int L,
 
 extern "C" int ap_init_conv_u(ap_ctx *ctx, const float *x, const float *part_t_layer0, void *u_out, int B, int L, void *stream) {
   if (!ctx || !ctx->loaded || !x || !part_t_layer0 || !u_out || B < 1 || L < 1) { set_error("ap_init_conv_u: bad argument"); return -22; }
-  if (!resblock_bf16u_serves(ctx, L)) { set_error("ap_init_conv_u: AP_PREC_BF16_STORE contexts with res = skip = 256 channels only"); return -22; }
+  if (!block_bf16u_serves(block_ask(ctx, 0, B, L))) { set_error("ap_init_conv_u: AP_PREC_BF16_STORE contexts with res = skip = 256 channels only"); return -22; }
   return launch_init_conv_u(ctx, x, part_t_layer0, u_out, B, L, (hipStream_t)stream);
 }
 
@@ -514,7 +478,7 @@ extern "C" int ap_resblock_fwd_u(ap_ctx *ctx, int layer, const void *u_in, const
                                  void *stream) {
   if (int e = check_block_args("ap_resblock_fwd_u", ctx, u_in && g_image, layer, B, L, u_in, "u_in", u_out, "u_out")) return e;
   if (u_out && !part_t_next) { set_error("ap_resblock_fwd_u: u_out needs the next layer's part_t"); return -22; }
-  return launch_resblock_u_timed(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream);
+  return launch_resblock_bf16u(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream);
 }
 
 extern "C" int ap_resblock_fwd(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
@@ -534,12 +498,12 @@ extern "C" int ap_resblock_fwd_u_save(ap_ctx *ctx, int layer, const void *u_in, 
                                       void *gate_factors, int B, int L, void *stream) {
   if (int e = check_block_args("ap_resblock_fwd_u_save", ctx, u_in && g_image && gate_factors, layer, B, L, u_in, "u_in", u_out, "u_out")) return e;
   if (u_out && !part_t_next) { set_error("ap_resblock_fwd_u_save: u_out needs the next layer's part_t"); return -22; }
-  return launch_resblock_u_timed(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream, gate_factors);
+  return launch_resblock_bf16u(ctx, layer, u_in, part_t_next, u_out, g_image, B, L, (hipStream_t)stream, gate_factors);
 }
 
 extern "C" size_t ap_gate_factor_bytes(int B, int L) {
   if (B < 1 || L < 1) return 0;
-  return (size_t)B * (size_t)((L + 127) / 128) * 131072u;
+  return (size_t)B * (size_t)((L + BLOCK_PT - 1) / BLOCK_PT) * BLOCK_FACTOR_TILE_BYTES;
 }
 
 extern "C" int ap_resblock_fwd_gate_save(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/audiopure.h"
+#include "ap_block_plan.h"   // the residual block's dispatch rule and the tile sizes it shares with the kernels (host-only)
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -44,15 +45,17 @@ inline int device_cu_count() {
 #define AP_ABLATE_PARAM , int ablate
 #define AP_ABLATE_ARG(x) , (x)
 #define AP_ABLATE_DECL
-#define AP_TOOLS_VAR static int
+extern BlockTune g_block_tune;   // (ap_kernels.hip) the one set of block-dispatch switches the ap_debug_* hooks write
+constexpr bool g_keep_plans = false;   // (the switches move under a context: plan every time)
 #else
 #define AP_ABLATE_PARAM
 #define AP_ABLATE_ARG(x)
 #define AP_ABLATE_DECL constexpr int ablate = 0;
-#define AP_TOOLS_VAR static constexpr int
+constexpr BlockTune g_block_tune{};
+constexpr bool g_keep_plans = true;
 #endif
 
-constexpr int TT = 128;   // time-tile (samples) of the fused kernels
+constexpr int TT = BLOCK_TT;   // time-tile (samples) of the fused kernels
 constexpr int KC = 32;    // channels per staged K-chunk of the dilated conv (x3 taps = 96 K rows)
 
 // Offsets (in floats) of the reference state-dict tensors inside the weight blob.
@@ -110,6 +113,10 @@ struct ap_ctx {
   std::vector<char> ev_kind;    // per pair: 0 residual-block launch, 1 skip-GEMM launch of the deferred-skip form
   size_t ev_used;
   int skip_group;               // AP_PREC_BF16: layers per skip GEMM of the deferred-skip form (0: fused block, skip per layer)
+  int n_cu;                     // CUs of the device the weights were loaded on (ap_ctx_load_wavenet): what the block plans read, not a runtime call per launch
+  std::vector<ap::BlockPlanSlot> plans;   // [NL][4] kept block plans (planned_block); with drop_*: emptied by forget_plans
+  int drop_B, drop_L, drop_defer;         // run_net's last (B, L, deferred skip?) and whether the last layer then drops h'
+  bool drop_last;
 };
 
 namespace ap {
@@ -140,6 +147,50 @@ struct ProfileSpan {
     return 0;
   }
 };
+
+// What block_plan reads, from a context and one call's arguments (hout: u' on the u-image interface)
+inline BlockAsk block_ask(const ap_ctx *ctx, int layer, int B, int L, bool hout = true, bool skip = true, bool aout = false, bool gout = false,
+                          bool fout = false, bool u = false) {
+  return BlockAsk{ctx->cfg.precision, ctx->C, ctx->S, ctx->NL, ctx->cfg.dilation_cycle, ctx->f32_form, ctx->w1w != nullptr, ctx->w1w_s != nullptr,
+                  ctx->w2p_bf != nullptr, ctx->wf1p_bf != nullptr, layer, B, L, ctx->n_cu, hout, skip, aout, gout, fout, u};
+}
+// a launcher's first step: the plan's return code, with the refusal's text set
+inline int plan_refused(int rc, const BlockPlan &p) {
+  if (rc) set_error(p.err, p.err_arg[0], p.err_arg[1], p.err_arg[2], p.err_arg[3]);
+  return rc;
+}
+// The plan of one block launch (rc: 0, or the refusal's code with its text set).  Kept in the context per (layer, h' asked, save asked)
+// and reused while the outputs asked, B and L repeat: a chain launches the same shapes step after step.  Refusals are not kept.
+// forget_plans: on reload and on an f32_form change.  The tools build, whose switches move under a context, plans every time.
+inline void forget_plans(ap_ctx *ctx) { ctx->plans.clear(); ctx->drop_B = 0; }
+inline const BlockPlan &planned_block(ap_ctx *ctx, int layer, int B, int L, bool hout, bool skip, bool aout, bool gout, bool fout, bool u, int *rc) {
+  const int key = hout | skip << 1 | aout << 2 | gout << 3 | fout << 4 | u << 5;
+  if (ctx->plans.empty()) ctx->plans.resize((size_t)ctx->NL * 4);
+  BlockPlanSlot &s = ctx->plans[(size_t)layer * 4 + (hout | (aout || fout) << 1)];
+  if (g_keep_plans && s.key == key && s.B == B && s.L == L) { *rc = 0; return s.plan; }
+  *rc = plan_refused(block_plan(block_ask(ctx, layer, B, L, hout, skip, aout, gout, fout, u), g_block_tune, &s.plan), s.plan);
+  s.key = *rc ? -1 : key; s.B = B; s.L = L;
+  return s.plan;
+}
+// bf16 persistent blocks: one buffer descriptor per parameter slab (the bf16 images; the fp32 biases), a layer's tensors at byte offsets
+struct BlockSlabs {
+  const char *wlo; unsigned wbytes, w1_off, w2_off;
+  const float *blo; unsigned bbytes, b1_off, b2_off;
+};
+inline BlockSlabs block_slabs(const ap_ctx *ctx, int layer) {
+  const int C = ctx->C, S = ctx->S;
+  const size_t n1 = (size_t)2 * C * C * 3, n2 = (size_t)(C + S) * C;
+  const char *w1 = (const char *)ctx->w1p_bf, *w2 = (const char *)ctx->w2p_bf;
+  const float *blo = ctx->b1 < ctx->b2 ? ctx->b1 : ctx->b2, *bhi = ctx->b1 < ctx->b2 ? ctx->b2 : ctx->b1;
+  BlockSlabs s{w1 < w2 ? w1 : w2, 0, 0, 0, blo, 0, 0, 0};
+  s.w1_off = (unsigned)(w1 - s.wlo + layer * n1 * 2);
+  s.w2_off = (unsigned)(w2 - s.wlo + layer * n2 * 2);
+  s.wbytes = (unsigned)(((size_t)ctx->NL * (n1 + n2) + (size_t)S * S) * 2);   // the whole bf16 slab
+  s.b1_off = (unsigned)((ctx->b1 - blo + (size_t)layer * 2 * C) * 4);
+  s.b2_off = (unsigned)((ctx->b2 - blo + (size_t)layer * (C + S)) * 4);
+  s.bbytes = (unsigned)((bhi - blo + (size_t)ctx->NL * 2 * C) * 4);
+  return s;
+}
 
 // What every block entry point of the C-ABI checks first (`who` is its name): the context is loaded and no required pointer is
 // null (`ptrs`), layer and shape are in range, the output does not alias the input.  0, or -22 with the error text set.
@@ -177,40 +228,27 @@ int launch_final_affine(ap_ctx *ctx, const float *skip, const float *x, float *e
 int launch_affine_noise(const float *x, float *out, float ca, float cs, const float *z, uint64_t seed,
                         uint32_t draw, uint64_t utt_offset, int B, int L, hipStream_t st);
 int launch_pack_bf16(ap_ctx *ctx, hipStream_t st);
-int launch_final_affine_bf16(ap_ctx *ctx, const float *skip, const float *x, float *eps_out, float *out, float ca, float cb,
-                             float cs, const float *z, uint64_t seed, uint32_t draw, uint64_t utt_offset, int B, int L,
-                             hipStream_t st);                    // returns 1 if the shape is not served (caller: fp32 kernel)
-// `gout` non-null: the deferred-skip form -- the block writes h' and its gate output as a bf16 image [clip][L][256] to gout and
-// leaves `skip` alone; launch_skipgemm_bf16 then adds a group of layers' skip_conv outputs in one GEMM (ap_skipgemm_bf16.hip)
-// ap_resblock_bf16s.hip: the deferred-skip block for launches of at most one 128-sample tile per CU (64-sample tiles, bit-identical results)
-bool resblock_bf16s_serves(const ap_ctx *ctx, int B, int L);
-int launch_resblock_bf16s(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, void *gout, int B, int L, hipStream_t st);
-int launch_resblock_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                         int accumulate, int B, int L, hipStream_t st, void *gout = nullptr, void *fout = nullptr);
-int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                          int accumulate, int B, int L, hipStream_t st, void *gout = nullptr, void *fout = nullptr);   // persistent form; returns 1 if the shape is not served
-                                                                  // (fout, with gout: + the gate's derivative factors, 128 KB per 128-sample tile)
-// AP_PREC_BF16_STORE (ap_resblock_bf16u.hip): the residual stream as bf16 images of u = h + part_t, [clip][C / 32][L][32]
-bool resblock_bf16u_serves(const ap_ctx *ctx, int L);
-int launch_init_conv_u(ap_ctx *ctx, const float *x, const float *pt0, void *u, int B, int L, hipStream_t st);
-bool resblock_bf16us_serves(const ap_ctx *ctx, int B, int L);     // AP_PREC_BF16_STORE, at most one 128-sample tile per CU: 64-sample tiles (ap_resblock_bf16us.hip)
-int launch_resblock_bf16us(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st);
+// The residual block: launch_resblock (fp32 tensors) and launch_resblock_bf16u (bf16 u images, AP_PREC_BF16_STORE; uout null: the net's
+// last layer) plan (ap_block_plan.h), time the launch (profile kind 0) and switch on the family; launch_block_* are the families' leaves.
+// `gout` non-null: the deferred-skip form -- the block writes h' and its gate output as a bf16 image [clip][L][256] to gout and leaves
+// `skip` alone (launch_skipgemm_bf16 adds a group of layers' skip_conv outputs in one GEMM); fout: + the gate's derivative factors
 int launch_resblock_bf16u(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st,
-                          void *fout = nullptr);                  // uout null: the net's last layer; fout: + the gate's derivative factors
+                          void *fout = nullptr);
+int launch_block_f32w(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                      hipStream_t st, float *aout);
+int launch_block_split(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                       hipStream_t st);
+int launch_block_split23(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                         hipStream_t st);
+int launch_block_bf16p(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                       hipStream_t st, void *gout, void *fout);
+int launch_block_bf16s(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, void *gout, int L, hipStream_t st);
+int launch_block_bf16us(ap_ctx *ctx, const BlockPlan &p, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int L, hipStream_t st);
+int launch_init_conv_u(ap_ctx *ctx, const float *x, const float *pt0, void *u, int B, int L, hipStream_t st);
 int launch_skipgemm_bf16(ap_ctx *ctx, int layer0, int nl, const void *gimg, float *skip, int accumulate, int B, int L, hipStream_t st);
-int launch_resblock_bf16w(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                          int accumulate, int B, int L, hipStream_t st);   // one wave per SIMD; returns 1 if the shape is not served
 int launch_pack_f32w(ap_ctx *ctx, hipStream_t st);
-bool resblock_f32w_serves(const ap_ctx *ctx, int B, int L);       // AP_PREC_F32 in minimal-filtering form, and this shape is built
-int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                         int accumulate, int B, int L, hipStream_t st, float *aout = nullptr);   // hout null: the net's last layer (no res_conv, no h'); returns 1 if the shape is not served
 int launch_pack_split(ap_ctx *ctx, hipStream_t st);
 int launch_pack_split23(ap_ctx *ctx, hipStream_t st);            // ap_resblock_f32s2.hip: AP_PREC_F32_SPLIT with the dilated conv in F(2,3) form
-bool resblock_split23_serves(const ap_ctx *ctx, int B, int L);
-int launch_resblock_split23(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int B, int L,
-                            hipStream_t st);
-int launch_resblock_split(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                          int accumulate, int B, int L, hipStream_t st);
 int prepare_bwd_f32(ap_ctx *ctx, hipStream_t st);                // ap_ctx_prepare_backward, per precision (allocate + pack + synchronise)
 int prepare_bwd_bf16(ap_ctx *ctx, hipStream_t st);
 // ap_conv_w3.hip: 3 x 3 / stride 1 / pad 1 / ungrouped layers in F(2,3) form along W (which layers: ap_conv_plan.h)

@@ -537,90 +537,51 @@ __global__ __launch_bounds__(C / 64 * TTK, 2) void resblock_f32_kernel(
   }
 }
 
-AP_TOOLS_VAR g_tile = 64;    // time tile of the residual-block kernel: 64 (4 waves, 2 WG/CU); 128 (8 waves, 1 WG/CU) in tools builds
-AP_TOOLS_VAR g_force_direct = 0;   // tools builds: the direct-form fp32 block even where the minimal-filtering one is built
-AP_TOOLS_VAR g_no_bf16s = 0;  // tools builds: 1 = small bf16 launches stay on the persistent kernel, 2 = every deferred-skip launch on ap_resblock_bf16s.hip (A/B, bit identity)
-AP_TOOLS_VAR g_force_f32 = 0;  // tools builds: run the fp32 kernel even in a bf16 context (A/B timing in one process)
 #ifdef AP_TOOLS
+BlockTune g_block_tune;        // the block-dispatch switches (ap_block_plan.h), written by the ap_debug_* hooks
 static int g_ablate = 0;       // timing-only ablation mask (ap_debug_ablate)
+// tools/csrc/ap_resblock_bf16.hip: kernels that are never planned, tried first where a switch asks; 1: the plan serves the launch
+int try_resblock_bf16_tools(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int B, int L, hipStream_t st);
 #endif
+
+// the direct-form fp32 block: exactly the instantiations the plan can name (C = 64 with SAVE: 64-sample tiles only; C = 128: no SAVE)
+static int launch_block_f32(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
+                            int L, hipStream_t st, float *aout) {
+  const int C = ctx->C, S = ctx->S;
+  const float *w1p = ctx->w1p + (size_t)layer * 2 * C * C * 3, *w2p = ctx->w2p + (size_t)layer * (C + S) * C;
+  const float *b1 = ctx->b1 + (size_t)layer * 2 * C, *b2 = ctx->b2 + (size_t)layer * (C + S);
+#define AP_RB(CC, TK, SV)                                                                                                       \
+  if (C == CC && p.tile == TK && p.save == SV)                                                                                  \
+    resblock_f32_kernel<CC, TK, SV><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, p.d, accumulate, p.ntiles, \
+                                                             SV ? aout : nullptr AP_ABLATE_ARG(g_ablate))
+  AP_RB(256, 64, true); AP_RB(256, 128, true); AP_RB(64, 64, true);
+  AP_RB(64, 64, false); AP_RB(64, 128, false); AP_RB(128, 64, false); AP_RB(128, 128, false); AP_RB(256, 64, false); AP_RB(256, 128, false);
+#undef AP_RB
+  AP_HIP(hipGetLastError());
+  return 0;
+}
 
 int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
                     int accumulate, int B, int L, hipStream_t st, float *aout, void *gout, void *fout) {
-  if (aout && ctx->cfg.precision != AP_PREC_F32) {
-    set_error("ap_resblock_fwd_save: AP_PREC_F32 only (the other modes recompute the pre-gate activations)");
-    return -22;
-  }
-  if (ctx->cfg.precision == AP_PREC_BF16_STORE) {
-    set_error("AP_PREC_BF16_STORE: the residual stream is a bf16 image in this mode (ap_init_conv_u / ap_resblock_fwd_u), not an fp32 tensor; "
-              "the fp32-tensor block serves AP_PREC_F32, AP_PREC_F32_SPLIT and AP_PREC_BF16");
-    return -22;
-  }
-  if (gout && (ctx->cfg.precision != AP_PREC_BF16 || g_force_f32)) {
-    set_error("deferred-skip form: AP_PREC_BF16 only");
-    return -22;
-  }
-  if (ctx->cfg.precision != AP_PREC_F32 && !g_force_f32) {
-    ProfileSpan span;
-    if (int e = span.begin(ctx, 0, st)) return e;
-    int rc = ctx->cfg.precision == AP_PREC_BF16
-                 ? (gout && !fout && g_no_bf16s != 1 && (g_no_bf16s == 2 || resblock_bf16s_serves(ctx, B, L))
-                        ? launch_resblock_bf16s(ctx, layer, hin, pt, hout, gout, B, L, st)     // small batches: half-size tiles, bit-identical
-                        : launch_resblock_bf16(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, gout, fout))
-                 : launch_resblock_split(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
-    if (int e = span.end()) return e;
-    return rc;
-  }
-  const int C = ctx->C, S = ctx->S;
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
-  if (!g_force_direct && resblock_f32w_serves(ctx, B, L)) {     // F(2,3) form of the dilated conv (ap_resblock_f32w.hip)
-    ProfileSpan span;
-    if (int e = span.begin(ctx, 0, st)) return e;
-    const int rcw = launch_resblock_f32w(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, aout);
-    if (int e = span.end()) return e;
-    return rcw;
-  }
-  if (!hout) {
-    set_error("resblock: the direct-form block needs an h' buffer");
-    return -22;
-  }
-  const float *w1p = ctx->w1p + (size_t)layer * 2 * C * C * 3;
-  const float *w2p = ctx->w2p + (size_t)layer * (C + S) * C;
-  const float *b1 = ctx->b1 + (size_t)layer * 2 * C;
-  const float *b2 = ctx->b2 + (size_t)layer * (C + S);
+  int refused;
+  const BlockPlan &p = planned_block(ctx, layer, B, L, hout, skip, aout, gout, fout, false, &refused);
+  if (refused) return refused;
   ProfileSpan span;
   if (int e = span.begin(ctx, 0, st)) return e;
-#define AP_RB(CC, TK)                                                                                              \
-  resblock_f32_kernel<CC, TK><<<(unsigned)B * ((L + TK - 1) / TK), CC / 64 * TK, 0, st>>>(                         \
-      hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, (L + TK - 1) / TK, nullptr AP_ABLATE_ARG(g_ablate))
-#define AP_RB_SAVE(CC, TK)                                                                                         \
-  resblock_f32_kernel<CC, TK, true><<<(unsigned)B * ((L + TK - 1) / TK), CC / 64 * TK, 0, st>>>(                   \
-      hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, (L + TK - 1) / TK, aout AP_ABLATE_ARG(g_ablate))
-  const int tk = g_tile;
-  if (aout) {
-    if (C == 256 && tk == 64) AP_RB_SAVE(256, 64);
-    else if (C == 256) AP_RB_SAVE(256, 128);
-    else if (C == 64) AP_RB_SAVE(64, 64);
-    else {
-      set_error("resblock (save): unsupported res_channels %d (need 64 or 256)", C);
-      return -22;
-    }
-  } else
-  if (C == 64 && tk == 64) AP_RB(64, 64);
-  else if (C == 64) AP_RB(64, 128);
-  else if (C == 128 && tk == 64) AP_RB(128, 64);
-  else if (C == 128) AP_RB(128, 128);
-  else if (C == 256 && tk == 64) AP_RB(256, 64);
-  else if (C == 256) AP_RB(256, 128);
-  else {
-    set_error("resblock: unsupported res_channels %d (need 64, 128 or 256)", C);
-    return -22;
+  int rc = 1;
+#ifdef AP_TOOLS
+  if (p.family == BLOCK_BF16_P && !gout) rc = try_resblock_bf16_tools(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
+#endif
+  if (rc == 1) switch (p.family) {
+    case BLOCK_F32_DIRECT: rc = launch_block_f32(ctx, p, layer, hin, pt, hout, skip, accumulate, L, st, aout); break;
+    case BLOCK_F32_F23: rc = launch_block_f32w(ctx, p, layer, hin, pt, hout, skip, accumulate, L, st, aout); break;
+    case BLOCK_SPLIT_DIRECT: rc = launch_block_split(ctx, p, layer, hin, pt, hout, skip, accumulate, L, st); break;
+    case BLOCK_SPLIT_F23: rc = launch_block_split23(ctx, p, layer, hin, pt, hout, skip, accumulate, L, st); break;
+    case BLOCK_BF16_P: rc = launch_block_bf16p(ctx, p, layer, hin, pt, hout, skip, accumulate, L, st, gout, fout); break;
+    default: rc = launch_block_bf16s(ctx, p, layer, hin, pt, hout, gout, L, st); break;   // BLOCK_BF16_S (the u families: launch_resblock_bf16u)
   }
-#undef AP_RB
-#undef AP_RB_SAVE
   if (int e = span.end()) return e;
-  AP_HIP(hipGetLastError());
-  return 0;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -924,41 +885,21 @@ __global__ __launch_bounds__(256, 2) void final_bf16_kernel(
   }
 }
 
-int launch_final_affine_bf16(ap_ctx *ctx, const float *skip, const float *x, float *eps_out, float *out, float ca, float cb,
-                             float cs, const float *z, uint64_t seed, uint32_t draw, uint64_t utt_offset, int B, int L,
-                             hipStream_t st) {
-  if (ctx->S != 256 || !ctx->wf1p_bf) return 1;
-  const int ntiles = (L + 63) / 64;
-  const float scale = (float)sqrt(1.0 / (double)ctx->NL);      // math.sqrt(1.0/N) (WaveNet.py:135)
-  final_bf16_kernel<<<(unsigned)B * ntiles, 256, 0, st>>>(skip, x, eps_out, out, (const fb16x8 *)ctx->wf1p_bf, ctx->bf1, ctx->wf2,
-                                                          ctx->bf2, scale, ca, cb, cs, z, seed, draw, utt_offset, L, ntiles);
-  AP_HIP(hipGetLastError());
-  return 0;
-}
-
 int launch_final_affine(ap_ctx *ctx, const float *skip, const float *x, float *eps_out, float *out, float ca,
                         float cb, float cs, const float *z, uint64_t seed, uint32_t draw, uint64_t utt_offset,
                         int B, int L, hipStream_t st) {
-  if (ctx->cfg.precision == AP_PREC_BF16 || ctx->cfg.precision == AP_PREC_BF16_STORE) {   // bf16 modes: the 1x1 convs of final_conv on the bf16 pipe as well
-    const int rc = launch_final_affine_bf16(ctx, skip, x, eps_out, out, ca, cb, cs, z, seed, draw, utt_offset, B, L, st);
-    if (rc != 1) return rc;
-  }
-  const int S = ctx->S;
-  const int ft = (S == 256) ? 64 : TT;
-  const int ntiles = (L + ft - 1) / ft;
-  const float scale = (float)sqrt(1.0 / (double)ctx->NL);   // math.sqrt(1.0/N) (WaveNet.py:135)
-  unsigned grid = (unsigned)B * ntiles;
-#define AP_FINAL(SS, FTV)                                                                                         \
-  final_f32_kernel<SS, FTV><<<grid, SS, 0, st>>>(skip, x, eps_out, out, ctx->wf1p, ctx->bf1, ctx->wf2, ctx->bf2,   \
-                                                 scale, ca, cb, cs, z, seed, draw, utt_offset, L, ntiles)
-  switch (S) {
-    case 64: AP_FINAL(64, 128); break;
-    case 128: AP_FINAL(128, 128); break;
-    case 256: AP_FINAL(256, 64); break;
-    default:
-      set_error("final: unsupported skip_channels %d", S);
-      return -22;
-  }
+  BlockPlan p;                                                   // bf16 modes: the 1x1 convs of final_conv on the bf16 pipe as well
+  if (int e = plan_refused(final_plan(block_ask(ctx, 0, B, L), &p), p)) return e;
+  const float scale = (float)sqrt(1.0 / (double)ctx->NL);      // math.sqrt(1.0/N) (WaveNet.py:135)
+#define AP_FINAL(SS, FTV)                                                                                                \
+  final_f32_kernel<SS, FTV><<<p.grid, p.wg, 0, st>>>(skip, x, eps_out, out, ctx->wf1p, ctx->bf1, ctx->wf2, ctx->bf2, scale, \
+                                                     ca, cb, cs, z, seed, draw, utt_offset, L, p.ntiles)
+  if (p.family == BLOCK_FINAL_BF16)
+    final_bf16_kernel<<<p.grid, p.wg, 0, st>>>(skip, x, eps_out, out, (const fb16x8 *)ctx->wf1p_bf, ctx->bf1, ctx->wf2, ctx->bf2, scale, ca, cb, cs, z,
+                                               seed, draw, utt_offset, L, p.ntiles);
+  else if (ctx->S == 64) AP_FINAL(64, BLOCK_TT);
+  else if (ctx->S == 128) AP_FINAL(128, BLOCK_TT);
+  else AP_FINAL(256, BLOCK_FT);
 #undef AP_FINAL
   AP_HIP(hipGetLastError());
   return 0;
@@ -1021,17 +962,17 @@ __global__ void philox_fill_kernel(float *__restrict__ out, uint64_t seed, uint3
 #ifdef AP_TOOLS
 extern "C" int ap_debug_tile(int tile) {
   if (tile != 64 && tile != 128) return -22;
-  ap::g_tile = tile;
+  ap::g_block_tune.tile = tile;
   return 0;
 }
 
 extern "C" int ap_debug_force_f32(int on) {
-  ap::g_force_f32 = on;
+  ap::g_block_tune.force_f32 = on;
   return 0;
 }
 
 extern "C" int ap_debug_no_bf16s(int on) {                       // 1: small bf16 launches stay on the persistent kernel
-  ap::g_no_bf16s = on;
+  ap::g_block_tune.no_bf16s = on;
   return 0;
 }
 

@@ -32,7 +32,7 @@ namespace ap {
 
 namespace {
 
-constexpr int PT_ = 128;                 // time tile
+constexpr int PT_ = BLOCK_PT;            // time tile
 constexpr int KC_ = 32;                  // channels per staged chunk -> 96 K rows = 6 k-steps of 16
 constexpr int PS_ = 32;                  // fp32 per row of the wave-private output patch (128 B)
 
@@ -783,81 +783,35 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16p_kernel(
   }
 }
 
-// -> 0 launched, 1 shape not served by this kernel (caller falls back to the per-tile kernel)
-int launch_resblock_bf16p(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
-                          int B, int L, hipStream_t st, void *gout, void *fout) {
-  const int C = ctx->C, S = ctx->S;
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
-  if (C != 256 || S != 256 || L < 1) return 1;
-  const bool rag = (L % 4) != 0;                                 // ragged clip length: the RAG instantiations
-  // staging form: one window for the three taps where they overlap (d <= 32), else three tap loads
-  const int ws = d == 1 ? 1 : d == 2 ? 2 : (d <= 32 && d % 4 == 0) ? 0 : d < 4 ? -2 : -1;
-  if (ws == -2) return 1;                                        // (d = 3: no such dilation in a power-of-two cycle)
-  const int n_cu = device_cu_count();                            // (the grid is one workgroup per CU)
-  const int ntiles = (L + PT_ - 1) / PT_;
-  const int nblk = B * ntiles;
-  int grid = nblk < n_cu ? nblk : n_cu;
-  if (grid >= 8) grid &= ~7;
-  // one descriptor per parameter slab, the per-layer tensors addressed by byte offsets inside it
-  const size_t n1 = (size_t)2 * C * C * 3, n2 = (size_t)(C + S) * C;
-  const char *wlo = (const char *)ctx->w1p_bf < (const char *)ctx->w2p_bf ? (const char *)ctx->w1p_bf : (const char *)ctx->w2p_bf;
-  const unsigned w1_off = (unsigned)((const char *)ctx->w1p_bf - wlo + layer * n1 * 2);
-  const unsigned w2_off = (unsigned)((const char *)ctx->w2p_bf - wlo + layer * n2 * 2);
-  const unsigned wbytes = (unsigned)(((size_t)ctx->NL * (n1 + n2) + (size_t)S * S) * 2);   // the whole bf16 slab
-  const float *blo = ctx->b1 < ctx->b2 ? ctx->b1 : ctx->b2;
-  const float *bhi = ctx->b1 < ctx->b2 ? ctx->b2 : ctx->b1;
-  const unsigned b1_off = (unsigned)((ctx->b1 - blo + (size_t)layer * 2 * C) * 4);
-  const unsigned b2_off = (unsigned)((ctx->b2 - blo + (size_t)layer * (C + S)) * 4);
-  const unsigned bbytes = (unsigned)((bhi - blo + (size_t)ctx->NL * 2 * C) * 4);
-  if (gout) {                                                    // deferred-skip form: h' + the bf16 g image, no skip GEMM in the block
-    if ((size_t)L * 512 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16: clip too long for the bf16 g image"); return -22; }
-    if (fout && (size_t)ntiles * 131072 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16: clip too long for the gate-factor image"); return -22; }
-  }
-  // one launch of staging form (WS, RAG); the block form follows from the outputs asked for: gout -> DS (skip and accumulate unused),
-  // + no hout -> NOH (the net's last layer), + fout -> SAVEF (the differentiable purifier's forward)
+// BLOCK_BF16_P: one launch of the planned staging form (WS, RAG) and block form: DS = the deferred-skip form (skip and accumulate unused),
+// + NOH (the net's last layer), + SAVEF (the differentiable purifier's forward).  One workgroup per CU.
+int launch_block_bf16p(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                       hipStream_t st, void *gout, void *fout) {
+  const BlockSlabs sl = block_slabs(ctx, layer);
   auto launch = [&](auto ws_tag, auto rag_tag) {
     constexpr int W = decltype(ws_tag)::value;
     constexpr bool R = decltype(rag_tag)::value;
     auto go = [&](auto *kernel) {
-      kernel<<<(unsigned)grid, 512, 0, st>>>(hin, pt, hout, gout ? nullptr : skip, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d,
-                                             gout ? 0 : accumulate, ntiles, nblk, fout, gout);
+      kernel<<<p.grid, p.wg, 0, st>>>(hin, pt, hout, p.ds ? nullptr : skip, sl.wlo, sl.wbytes, sl.w1_off, sl.w2_off, sl.blo, sl.bbytes, sl.b1_off, sl.b2_off,
+                                      L, p.d, p.ds ? 0 : accumulate, p.ntiles, (int)p.nblk, fout, gout);
     };
-    if (!gout) go(resblock_bf16p_kernel<W, R>);
-    else if (fout && hout) go(resblock_bf16p_kernel<W, R, true, false, true>);
-    else if (fout) go(resblock_bf16p_kernel<W, R, true, true, true>);
-    else if (hout) go(resblock_bf16p_kernel<W, R, true>);
+    if (!p.ds) go(resblock_bf16p_kernel<W, R>);
+    else if (p.savef && !p.noh) go(resblock_bf16p_kernel<W, R, true, false, true>);
+    else if (p.savef) go(resblock_bf16p_kernel<W, R, true, true, true>);
+    else if (!p.noh) go(resblock_bf16p_kernel<W, R, true>);
     else go(resblock_bf16p_kernel<W, R, true, true>);
   };
   using std::integral_constant;
-  if (rag) {                                                     // (d = 4 .. 32 ragged: the three-tap form, one instantiation fewer)
-    if (ws == 1) launch(integral_constant<int, 1>{}, std::true_type{});
-    else if (ws == 2) launch(integral_constant<int, 2>{}, std::true_type{});
+  if (p.rag) {                                                   // (ragged: no one-window form at d = 4 .. 32)
+    if (p.ws == 1) launch(integral_constant<int, 1>{}, std::true_type{});
+    else if (p.ws == 2) launch(integral_constant<int, 2>{}, std::true_type{});
     else launch(integral_constant<int, -1>{}, std::true_type{});
-  } else if (ws == 0) launch(integral_constant<int, 0>{}, std::false_type{});
-  else if (ws == 1) launch(integral_constant<int, 1>{}, std::false_type{});
-  else if (ws == 2) launch(integral_constant<int, 2>{}, std::false_type{});
+  } else if (p.ws == 0) launch(integral_constant<int, 0>{}, std::false_type{});
+  else if (p.ws == 1) launch(integral_constant<int, 1>{}, std::false_type{});
+  else if (p.ws == 2) launch(integral_constant<int, 2>{}, std::false_type{});
   else launch(integral_constant<int, -1>{}, std::false_type{});
   AP_HIP(hipGetLastError());
   return 0;
 }
-
-#ifndef AP_TOOLS
-// AP_PREC_BF16 dispatch of the product library: the persistent kernel serves every shape of the supported configuration
-// (C = S = 256; any dilation of a power-of-two cycle, any clip length).  The one-tile-per-workgroup kernel of round 1
-// (tools/csrc/ap_resblock_bf16.hip) is compiled into the tools library only, as the A/B baseline of tools/cmp_bf16_kernels.py.
-int launch_resblock_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
-                         int B, int L, hipStream_t st, void *gout, void *fout) {
-  if (ctx->C != 256 || ctx->S != 256) {
-    set_error("AP_PREC_BF16 is built for res_channels = skip_channels = 256 only (got %d / %d)", ctx->C, ctx->S);
-    return -22;
-  }
-  const int rc = launch_resblock_bf16p(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, gout, fout);
-  if (rc == 1) {
-    set_error("AP_PREC_BF16: shape not served (layer %d, L = %d)", layer, L);
-    return -22;
-  }
-  return rc;
-}
-#endif
 
 }  // namespace ap

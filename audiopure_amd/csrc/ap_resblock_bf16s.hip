@@ -213,24 +213,16 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16s_kernel(const float *__r
                                             rowoff(r, 0) * L * 4, 0);
 }
 
-// at most one 128-sample tile per CU: the launches whose duration is one tile's latency on the persistent kernel
-bool resblock_bf16s_serves(const ap_ctx *ctx, int B, int L) {
-  if (ctx->cfg.precision != AP_PREC_BF16 || ctx->C != SC_ || ctx->S != SC_) return false;
-  if ((size_t)L * 1024 >= ((size_t)1 << 31)) return false;
-  return (long long)B * ((L + 127) / 128) <= 256;
-}
-
-int launch_resblock_bf16s(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, void *gout, int B, int L, hipStream_t st) {
+// BLOCK_BF16_S: launches of at most one 128-sample tile per CU, whose duration on the persistent kernel is one tile's latency
+int launch_block_bf16s(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, void *gout, int L, hipStream_t st) {
   const int C = SC_;
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
   const size_t n1 = (size_t)2 * C * C * 3, n2 = (size_t)(C + C) * C;
   const __bf16 *w1 = (const __bf16 *)ctx->w1p_bf + (size_t)layer * n1, *w2 = (const __bf16 *)ctx->w2p_bf + (size_t)layer * n2;
   const float *b1 = ctx->b1 + (size_t)layer * 2 * C, *b2 = ctx->b2 + (size_t)layer * 2 * C;
-  const int nt = (L + 63) / 64;
-  if (hout)
-    resblock_bf16s_kernel<false><<<(unsigned)(B * nt), 512, 0, st>>>(hin, pt, hout, gout, w1, w2, b1, b2, L, d, nt);
+  if (!p.noh)
+    resblock_bf16s_kernel<false><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, gout, w1, w2, b1, b2, L, p.d, p.ntiles);
   else
-    resblock_bf16s_kernel<true><<<(unsigned)(B * nt), 512, 0, st>>>(hin, pt, nullptr, gout, w1, w2, b1, b2, L, d, nt);
+    resblock_bf16s_kernel<true><<<p.grid, p.wg, 0, st>>>(hin, pt, nullptr, gout, w1, w2, b1, b2, L, p.d, p.ntiles);
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -34,7 +34,7 @@ namespace ap {
 
 namespace {
 
-constexpr int PT_ = 128;                 // time tile
+constexpr int PT_ = BLOCK_PT;            // time tile
 constexpr int KC_ = 32;                  // channels per chunk -> 96 K rows = 6 k-steps of 16
 
 }  // namespace
@@ -498,56 +498,30 @@ __global__ __launch_bounds__(512, 2) void resblock_bf16u_kernel(
   }
 }
 
-bool resblock_bf16u_serves(const ap_ctx *ctx, int L) {
-  return ctx->cfg.precision == AP_PREC_BF16_STORE && ctx->C == 256 && ctx->S == 256 && L >= 1 &&
-         (size_t)L * 512 < ((size_t)1 << 31);
-}
-
-// uout null: the net's last layer (no res_conv, no image out)
+// The u-image entry (uout null: the net's last layer; fout: + the gate's derivative factors): plan, time the launch, switch on the family
 int launch_resblock_bf16u(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st,
                           void *fout) {
-  if (!resblock_bf16u_serves(ctx, L)) {
-    set_error("AP_PREC_BF16_STORE: built for res = skip = 256 channels, clips shorter than 2^22 samples (got %d / %d, L = %d)", ctx->C, ctx->S, L);
-    return -22;
+  int refused;
+  const BlockPlan &p = planned_block(ctx, layer, B, L, uout, false, false, gout, fout, true, &refused);
+  if (refused) return refused;
+  ProfileSpan span;
+  if (int e = span.begin(ctx, 0, st)) return e;
+  int rc = 0;
+  if (p.family == BLOCK_BF16U_S) rc = launch_block_bf16us(ctx, p, layer, uin, pt_next, uout, gout, L, st);
+  else {                                                         // BLOCK_BF16U_P: one workgroup per CU
+    const BlockSlabs sl = block_slabs(ctx, layer);
+    auto go = [&](auto *kernel) {
+      kernel<<<p.grid, p.wg, 0, st>>>(uin, p.noh ? nullptr : uout, p.noh ? nullptr : pt_next, sl.wlo, sl.wbytes, sl.w1_off, sl.w2_off, sl.blo, sl.bbytes,
+                                      sl.b1_off, sl.b2_off, L, p.d, p.ntiles, (int)p.nblk, gout, fout);
+    };
+    if (p.savef && !p.noh) go(resblock_bf16u_kernel<false, true>);
+    else if (p.savef) go(resblock_bf16u_kernel<true, true>);
+    else if (!p.noh) go(resblock_bf16u_kernel<false>);
+    else go(resblock_bf16u_kernel<true>);
+    if (hipError_t e = hipGetLastError()) rc = hip_fail(e, "resblock_bf16u_kernel");
   }
-  // launches of at most one tile per CU (one- and two-clip calls): 64-sample tiles on twice as many workgroups, bit-identical results
-  if (!fout && resblock_bf16us_serves(ctx, B, L)) return launch_resblock_bf16us(ctx, layer, uin, pt_next, uout, gout, B, L, st);
-  const int C = ctx->C, S = ctx->S;
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
-  const int n_cu = device_cu_count();
-  const int ntiles = (L + PT_ - 1) / PT_;
-  const int nblk = B * ntiles;
-  int grid = nblk < n_cu ? nblk : n_cu;
-  if (grid >= 8) grid &= ~7;
-  const size_t n1 = (size_t)2 * C * C * 3, n2 = (size_t)(C + S) * C;
-  const char *wlo = (const char *)ctx->w1p_bf < (const char *)ctx->w2p_bf ? (const char *)ctx->w1p_bf : (const char *)ctx->w2p_bf;
-  const unsigned w1_off = (unsigned)((const char *)ctx->w1p_bf - wlo + layer * n1 * 2);
-  const unsigned w2_off = (unsigned)((const char *)ctx->w2p_bf - wlo + layer * n2 * 2);
-  const unsigned wbytes = (unsigned)(((size_t)ctx->NL * (n1 + n2) + (size_t)S * S) * 2);
-  const float *blo = ctx->b1 < ctx->b2 ? ctx->b1 : ctx->b2;
-  const float *bhi = ctx->b1 < ctx->b2 ? ctx->b2 : ctx->b1;
-  const unsigned b1_off = (unsigned)((ctx->b1 - blo + (size_t)layer * 2 * C) * 4);
-  const unsigned b2_off = (unsigned)((ctx->b2 - blo + (size_t)layer * (C + S)) * 4);
-  const unsigned bbytes = (unsigned)((bhi - blo + (size_t)ctx->NL * 2 * C) * 4);
-  if (fout) {                                                    // the differentiable purifier's forward: + the gate's derivative factors
-    if ((size_t)ntiles * 131072 >= ((size_t)1 << 31)) { set_error("AP_PREC_BF16_STORE: clip too long for the gate-factor image"); return -22; }
-    if (uout)
-      resblock_bf16u_kernel<false, true><<<(unsigned)grid, 512, 0, st>>>(uin, uout, pt_next, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off,
-                                                                            L, d, ntiles, nblk, gout, fout);
-    else
-      resblock_bf16u_kernel<true, true><<<(unsigned)grid, 512, 0, st>>>(uin, nullptr, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off,
-                                                                           L, d, ntiles, nblk, gout, fout);
-    AP_HIP(hipGetLastError());
-    return 0;
-  }
-  if (uout)
-    resblock_bf16u_kernel<false><<<(unsigned)grid, 512, 0, st>>>(uin, uout, pt_next, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d,
-                                                                 ntiles, nblk, gout);
-  else
-    resblock_bf16u_kernel<true><<<(unsigned)grid, 512, 0, st>>>(uin, nullptr, nullptr, wlo, wbytes, w1_off, w2_off, blo, bbytes, b1_off, b2_off, L, d,
-                                                                ntiles, nblk, gout);
-  AP_HIP(hipGetLastError());
-  return 0;
+  if (int e = span.end()) return e;
+  return rc;
 }
 
 }  // namespace ap

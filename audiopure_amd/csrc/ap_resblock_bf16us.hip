@@ -217,31 +217,16 @@ __global__ __launch_bounds__(512, 4) void resblock_bf16us_kernel(const void *__r
   }
 }
 
-#ifdef AP_TOOLS
-static int g_no_bf16us = 0;     // 1: small launches stay on the persistent kernel; 2: every launch without factors on this one (A/B, bit identity)
-#else
-static constexpr int g_no_bf16us = 0;
-#endif
-
-// at most one 128-sample tile per CU: the launches whose duration is one tile's latency on the persistent kernel
-bool resblock_bf16us_serves(const ap_ctx *ctx, int B, int L) {
-  if (ctx->cfg.precision != AP_PREC_BF16_STORE || ctx->C != UC_ || ctx->S != UC_ || g_no_bf16us == 1) return false;
-  if ((size_t)L * 512 >= ((size_t)1 << 31)) return false;
-  return g_no_bf16us == 2 || (long long)B * ((L + 127) / 128) <= 256;
-}
-
-int launch_resblock_bf16us(ap_ctx *ctx, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int B, int L, hipStream_t st) {
+// BLOCK_BF16U_S: launches of at most one 128-sample tile per CU, whose duration on the persistent kernel is one tile's latency
+int launch_block_bf16us(ap_ctx *ctx, const BlockPlan &p, int layer, const void *uin, const float *pt_next, void *uout, void *gout, int L, hipStream_t st) {
   const int C = UC_;
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
   const size_t n1 = (size_t)2 * C * C * 3, n2 = (size_t)(C + C) * C;
   const __bf16 *w1 = (const __bf16 *)ctx->w1p_bf + (size_t)layer * n1, *w2 = (const __bf16 *)ctx->w2p_bf + (size_t)layer * n2;
   const float *b1 = ctx->b1 + (size_t)layer * 2 * C, *b2 = ctx->b2 + (size_t)layer * 2 * C;
-  const int nt = (L + 63) / 64;
-  if ((long long)B * nt >= (1ll << 31)) { set_error("AP_PREC_BF16_STORE: too many tiles"); return -22; }
-  if (uout)
-    resblock_bf16us_kernel<false><<<(unsigned)(B * nt), 512, 0, st>>>(uin, uout, pt_next, gout, w1, w2, b1, b2, L, d, nt);
+  if (!p.noh)
+    resblock_bf16us_kernel<false><<<p.grid, p.wg, 0, st>>>(uin, uout, pt_next, gout, w1, w2, b1, b2, L, p.d, p.ntiles);
   else
-    resblock_bf16us_kernel<true><<<(unsigned)(B * nt), 512, 0, st>>>(uin, nullptr, nullptr, gout, w1, w2, b1, b2, L, d, nt);
+    resblock_bf16us_kernel<true><<<p.grid, p.wg, 0, st>>>(uin, nullptr, nullptr, gout, w1, w2, b1, b2, L, p.d, p.ntiles);
   AP_HIP(hipGetLastError());
   return 0;
 }
@@ -250,7 +235,7 @@ int launch_resblock_bf16us(ap_ctx *ctx, int layer, const void *uin, const float 
 
 #ifdef AP_TOOLS
 extern "C" int ap_debug_no_bf16us(int on) {
-  ap::g_no_bf16us = on;
+  ap::g_block_tune.no_bf16us = on;
   return 0;
 }
 #endif

@@ -19,7 +19,7 @@
 namespace ap {
 
 namespace f32s {
-constexpr int BT = 128;                  // time tile
+constexpr int BT = BLOCK_BT;             // time tile
 constexpr int BKC = 16;                  // channels per staged chunk -> 48 K rows = 3 k-steps (one per tap)
 constexpr int XS = 3 * BKC + 8;          // bf16 per column row of an X image (112 B: conflict-free b128 reads)
 constexpr int HT = 64;                   // columns per gate/GEMM2 half
@@ -451,34 +451,21 @@ __global__ __launch_bounds__(C / 32 * 64, 2) void resblock_f32s_kernel(
 extern unsigned long long *g_trace_bf16;
 #endif
 
-int launch_resblock_split(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                          int accumulate, int B, int L, hipStream_t st) {
-  const int C = ctx->C, S = ctx->S;
-  if (C != 256 || S != 256) {
-    set_error("AP_PREC_F32_SPLIT is built for res_channels = skip_channels = 256 only (got %d, %d)", C, S);
-    return -22;
-  }
-  // the dilated conv in F(2,3) form where built and selected (ap_resblock_f32s2.hip: 3/4 of this kernel's matrix work)
-  if (hout && resblock_split23_serves(ctx, B, L)) return launch_resblock_split23(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
-  const int d = 1 << (layer % ctx->cfg.dilation_cycle);
-  const int ntiles = (L + BT - 1) / BT;
-  const int nblk = B * ntiles;
-  const __bf16 *w1p = (const __bf16 *)ctx->w1p_s + (size_t)layer * 2 * C * C * 3 * 3;
-  const __bf16 *w2p = (const __bf16 *)ctx->w2p_s + (size_t)layer * (C + S) * C * 3;
-  const float *b1 = ctx->b1 + (size_t)layer * 2 * C;
-  const float *b2 = ctx->b2 + (size_t)layer * (C + S);
+// BLOCK_SPLIT_DIRECT: the aligned form (16-byte epilogue) or the ragged one, as planned
+int launch_block_split(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                       hipStream_t st) {
+  const int C = ctx->C, S = ctx->S, d = p.d, ntiles = p.ntiles, nblk = (int)p.nblk;
+  const __bf16 *w1p = (const __bf16 *)ctx->w1p_s + (size_t)layer * 2 * C * C * 3 * 3, *w2p = (const __bf16 *)ctx->w2p_s + (size_t)layer * (C + S) * C * 3;
+  const float *b1 = ctx->b1 + (size_t)layer * 2 * C, *b2 = ctx->b2 + (size_t)layer * (C + S);
 #ifdef AP_TOOLS
-  if (L % 4 == 0 && L >= 4 && g_trace_bf16)
-    resblock_f32s_kernel<256, true, true><<<(unsigned)nblk, 512, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d,
-                                                                         accumulate, ntiles, nblk, g_trace_bf16);
+  if (p.e4 && g_trace_bf16)
+    resblock_f32s_kernel<256, true, true><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, ntiles, nblk, g_trace_bf16);
   else
 #endif
-  if (L % 4 == 0 && L >= 4)
-    resblock_f32s_kernel<256, true, false><<<(unsigned)nblk, 512, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d,
-                                                                          accumulate, ntiles, nblk, nullptr);
+  if (p.e4)
+    resblock_f32s_kernel<256, true, false><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, ntiles, nblk, nullptr);
   else
-    resblock_f32s_kernel<256, false, false><<<(unsigned)nblk, 512, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d,
-                                                                           accumulate, ntiles, nblk, nullptr);
+    resblock_f32s_kernel<256, false, false><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1p, b1, w2p, b2, L, d, accumulate, ntiles, nblk, nullptr);
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -36,13 +36,13 @@ namespace ap {
 namespace {
 
 constexpr int C2_ = 256;                 // res = skip channels
-constexpr int NPT_ = 64;                 // pairs per K1 tile (128 outputs)
+constexpr int NPT_ = BLOCK_NPT;          // pairs per K1 tile (128 outputs)
 constexpr int KC1_ = 32;                 // input channels per K1 chunk: 4 products x 32 = 128 K rows = 8 k-steps (96 MFMAs per wave: a chunk
                                          // must outlast the memory latency of the next chunk's loads; 16-channel chunks did not: 26 ms per launch)
 constexpr int XS1_ = 4 * KC1_ + 8;       // bf16 per pair-column row of a K1 X image (272 B: conflict-free ds_read_b128 / ds_write_b128)
 constexpr int XIMG1_ = NPT_ * XS1_ * 2;  // 17,408 B per split image
 constexpr int XBUF1_ = 3 * XIMG1_;       // three splits per buffer
-constexpr int BT2_ = 128;                // K2 time tile
+constexpr int BT2_ = BLOCK_BT2;         // K2 time tile
 constexpr int KC2_ = 64;                 // g channels per K2 chunk = 4 k-steps (192 MFMAs per wave)
 constexpr int XS2_ = KC2_ + 8;           // bf16 per column row of a K2 g image (144 B: conflict-free ds_read_b128)
 constexpr int XIMG2_ = BT2_ * XS2_ * 2;  // 18,432 B per split image
@@ -408,26 +408,14 @@ __global__ __launch_bounds__(512, 2) void f32s_out_kernel(const float *__restric
   }
 }
 
-bool resblock_split23_serves(const ap_ctx *ctx, int B, int L) {
-  if (ctx->cfg.precision != AP_PREC_F32_SPLIT || ctx->C != C2_ || ctx->S != C2_ || ctx->f32_form != 1 || !ctx->w1w_s) return false;
-  if ((size_t)C2_ * (size_t)L * 4 >= ((size_t)1 << 31)) return false;       // a clip's rows must stay below the buffer descriptor's range
-  return (long long)B * ((L + 63) / 64 + 2) * 2 < (1ll << 31);
-}
-
-int launch_resblock_split23(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int B, int L,
-                            hipStream_t st) {
+// BLOCK_SPLIT_F23: the gate launch over pair tiles (two row halves each), then the output launch over time tiles
+int launch_block_split23(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                         hipStream_t st) {
   const int C = C2_;
-  const int logd = layer % ctx->cfg.dilation_cycle;
-  const long long d = 1ll << logd;
-  const long long np = (L / (2 * d)) * d + ((L % (2 * d)) < d ? (L % (2 * d)) : d);      // pairs whose first output is inside the clip
-  const int nt1 = (int)((np + NPT_ - 1) / NPT_);
-  const int nblk1 = B * nt1 * 2;
   const __bf16 *w1w = (const __bf16 *)ctx->w1w_s + (size_t)layer * 4 * 2 * C * C * 3;
   const __bf16 *w2p = (const __bf16 *)ctx->w2p_s + (size_t)layer * 2 * C * C * 3;
-  f32s_gate_kernel<<<(unsigned)nblk1, 512, 0, st>>>(hin, pt, hout, w1w, ctx->b1 + (size_t)layer * 2 * C, L, logd, (int)np, nt1, nblk1);
-  const int nt2 = (L + BT2_ - 1) / BT2_;
-  const int nblk2 = B * nt2;
-  f32s_out_kernel<<<(unsigned)nblk2, 512, 0, st>>>(hin, pt, hout, skip, w2p, ctx->b2 + (size_t)layer * 2 * C, L, accumulate, nt2, nblk2);
+  f32s_gate_kernel<<<p.grid, p.wg, 0, st>>>(hin, pt, hout, w1w, ctx->b1 + (size_t)layer * 2 * C, L, p.logd, (int)p.np, p.ntiles, (int)p.nblk);
+  f32s_out_kernel<<<p.grid2, p.wg, 0, st>>>(hin, pt, hout, skip, w2p, ctx->b2 + (size_t)layer * 2 * C, L, accumulate, p.ntiles2, (int)p.nblk2);
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -33,7 +33,7 @@ namespace ap {
 namespace {
 
 constexpr int WC_ = 256;                 // res = skip channels
-constexpr int NP_ = 32;                  // pairs per tile
+constexpr int NP_ = BLOCK_NP;            // pairs per tile
 constexpr int KCW_ = 32;                 // channels per staged chunk
 constexpr int NCH_ = WC_ / KCW_;         // 8 chunks
 constexpr int XS_ = KCW_ + 4;            // floats per (product, column) row of the X image
@@ -898,68 +898,36 @@ __global__ __launch_bounds__(256, 1) void resblock_f32w_kernel(
 #ifdef AP_TOOLS
 // the DIET masks the tools build instantiates beside the product's (each item alone on top of its predecessor's product mask)
 #define AP_F32W_AB_MASKS(X) X(0) X(2) X(4) X(6) X(22) X(54) X(150) X(182) X(1206)
-static int g_no_q16 = 0;                                        // ap_debug_f32w_q16(0): the 4-byte epilogue for every clip length (A/B)
-static int g_diet = AP_F32W_DIET;                               // ap_debug_f32w_diet(mask): the h'-writing Q16 block with another DIET mask (A/B)
-#else
-static constexpr int g_no_q16 = 0;
 #endif
 
 // one 16-byte form at DIET mask M; with DIET_QUAD_ the instantiation of the layer's dilation class
 template <bool NOH, bool SAVE, int M, class... A>
-static void launch_q16(unsigned grid, hipStream_t st, int logd, A... args) {
+static void launch_q16(unsigned grid, unsigned wg, hipStream_t st, int dcls, A... args) {
   if constexpr ((M & DIET_QUAD_) != 0) {
-    if (logd == 0) return resblock_f32w_kernel<NOH, SAVE, true, M, 1><<<grid, 256, 0, st>>>(args...);
-    if (logd == 1) return resblock_f32w_kernel<NOH, SAVE, true, M, 2><<<grid, 256, 0, st>>>(args...);
+    if (dcls == 1) return resblock_f32w_kernel<NOH, SAVE, true, M, 1><<<grid, wg, 0, st>>>(args...);
+    if (dcls == 2) return resblock_f32w_kernel<NOH, SAVE, true, M, 2><<<grid, wg, 0, st>>>(args...);
   }
-  resblock_f32w_kernel<NOH, SAVE, true, M><<<grid, 256, 0, st>>>(args...);
+  resblock_f32w_kernel<NOH, SAVE, true, M><<<grid, wg, 0, st>>>(args...);
 }
 
-bool resblock_f32w_serves(const ap_ctx *ctx, int B, int L) {
-  if (ctx->cfg.precision != AP_PREC_F32 || ctx->f32_form != 1 || ctx->C != WC_ || ctx->S != WC_ || !ctx->w1w) return false;
-  if ((size_t)2 * WC_ * (size_t)L * 4 >= ((size_t)1 << 31)) return false;   // (the pre-gate rows of the SAVE form: 2C rows per clip)
-  return (long long)B * ((L + 2 * NP_ - 1) / (2 * NP_) + 1) < (1ll << 31);
-}
-
-// returns 1 if the shape is not served (caller: the direct-form kernel)
-int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
-                         int B, int L, hipStream_t st, float *aout) {
-  if (!resblock_f32w_serves(ctx, B, L)) return 1;
-  const int g_ncu = device_cu_count();
-  const int logd = layer % ctx->cfg.dilation_cycle;
-  const long long d = 1ll << logd;
-  const long long np = (L / (2 * d)) * d + ((L % (2 * d)) < d ? (L % (2 * d)) : d);      // pairs whose first output is inside the clip
-  const int ntiles = (int)((np + NP_ - 1) / NP_);
-  const long long nblk = (long long)B * ntiles;
-  if (nblk >= (1ll << 31)) return 1;
-  const int C = ctx->C, S = ctx->S;
-  const float *w1w = ctx->w1w + (size_t)layer * 4 * 2 * C * C;
-  const float *w2w = ctx->w2w + (size_t)layer * (C + S) * C;
-  const float *b1 = ctx->b1 + (size_t)layer * 2 * C;
-  const float *b2 = ctx->b2 + (size_t)layer * (C + S);
-  const unsigned grid = (unsigned)(nblk < g_ncu ? nblk : g_ncu);
-  const bool q16 = (L & 3) == 0 && !g_no_q16;
-  if (aout) {
-    if (!hout) { set_error("resblock (save): needs an h' buffer"); return -22; }
-    if (q16) launch_q16<false, true, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
-    else resblock_f32w_kernel<false, true, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, aout);
-    AP_HIP(hipGetLastError());
-    return 0;
-  }
+// BLOCK_F32_F23: NOH / SAVE / 16-byte / quad-class / DIET mask as planned
+int launch_block_f32w(ap_ctx *ctx, const BlockPlan &p, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate, int L,
+                      hipStream_t st, float *aout) {
+  const int C = ctx->C, S = ctx->S, logd = p.logd, ntiles = p.ntiles, nblk = (int)p.nblk;
+  const float *w1w = ctx->w1w + (size_t)layer * 4 * 2 * C * C, *w2w = ctx->w2w + (size_t)layer * (C + S) * C;
+  const float *b1 = ctx->b1 + (size_t)layer * 2 * C, *b2 = ctx->b2 + (size_t)layer * (C + S);
+  float *const none = nullptr;
+  if (p.save && p.q16) launch_q16<false, true, AP_F32W_DIET>(p.grid, p.wg, st, p.dcls, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, aout);
+  else if (p.save) resblock_f32w_kernel<false, true, false, DIET4_><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, aout);
 #ifdef AP_TOOLS
-#define AP_F32W_AB(M)                                                                                                             \
-  if (hout && q16 && g_diet == M) {                                                                                               \
-    launch_q16<false, false, M>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk,    \
-                                (float *)nullptr);                                                                                \
-    AP_HIP(hipGetLastError());                                                                                                    \
-    return 0;                                                                                                                     \
-  }
+#define AP_F32W_AB(M) else if (p.diet == M) launch_q16<false, false, M>(p.grid, p.wg, st, p.dcls, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, none);
   AP_F32W_AB_MASKS(AP_F32W_AB)
 #undef AP_F32W_AB
 #endif
-  if (hout && q16) launch_q16<false, false, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, (float *)nullptr);
-  else if (hout) resblock_f32w_kernel<false, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
-  else if (q16) launch_q16<true, false, AP_F32W_DIET>(grid, st, logd, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, (float *)nullptr);
-  else resblock_f32w_kernel<true, false, false, DIET4_><<<grid, 256, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, (int)nblk, nullptr);
+  else if (!p.noh && p.q16) launch_q16<false, false, AP_F32W_DIET>(p.grid, p.wg, st, p.dcls, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, none);
+  else if (!p.noh) resblock_f32w_kernel<false, false, false, DIET4_><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, nullptr);
+  else if (p.q16) launch_q16<true, false, AP_F32W_DIET>(p.grid, p.wg, st, p.dcls, hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, none);
+  else resblock_f32w_kernel<true, false, false, DIET4_><<<p.grid, p.wg, 0, st>>>(hin, pt, hout, skip, w1w, b1, w2w, b2, L, logd, accumulate, ntiles, nblk, nullptr);
   AP_HIP(hipGetLastError());
   return 0;
 }
@@ -968,14 +936,15 @@ int launch_resblock_f32w(ap_ctx *ctx, int layer, const float *hin, const float *
 
 #ifdef AP_TOOLS
 extern "C" int ap_debug_f32w_q16(int on) {
-  ap::g_no_q16 = on ? 0 : 1;
+  ap::g_block_tune.no_q16 = on ? 0 : 1;
   return 0;
 }
 // the block's launch as the chains call it: h_out NULL = the last layer's form (no per-block entry point of include/audiopure.h reaches
-// it), pre_gate non-NULL = the SAVE form
+// it), pre_gate non-NULL = the SAVE form; 1: this context's block is not the minimal-filtering one
 extern "C" int ap_debug_resblock_f32w(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out, float *skip,
                                       int accumulate, int B, int L, void *stream, float *pre_gate) {
-  return ap::launch_resblock_f32w(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
+  if (!ap::block_f32w_serves(ap::block_ask(ctx, layer, B, L))) return 1;
+  return ap::launch_resblock(ctx, layer, h_in, part_t_layer, h_out, skip, accumulate, B, L, (hipStream_t)stream, pre_gate);
 }
 // the h'-writing 16-byte form (what the headline runs 175 of 180 launches on) with the product's DIET mask or one of AP_F32W_AB_MASKS
 // (54 = 22 + pairs, 150 = 22 + no zeroing, 182 = both: the product before the seamless chunk turn); every other form keeps
@@ -986,7 +955,7 @@ extern "C" int ap_debug_f32w_diet(int mask) {
   AP_F32W_AB_MASKS(AP_F32W_KNOWN)
 #undef AP_F32W_KNOWN
   if (!known) return -22;
-  ap::g_diet = mask;
+  ap::g_block_tune.diet = mask == AP_F32W_DIET ? -1 : mask;
   return 0;
 }
 #endif

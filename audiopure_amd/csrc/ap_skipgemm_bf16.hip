@@ -27,7 +27,7 @@ namespace ap {
 
 namespace {
 
-constexpr int SPT = 128;                  // time tile
+constexpr int SPT = BLOCK_SPT;            // time tile
 constexpr int SGS = 256 + 8;              // bf16 per column row of the g image in LDS (528 B)
 constexpr int SPS = 32;                   // fp32 per row of the wave-private output patch (128 B)
 
@@ -260,28 +260,21 @@ extern int g_skipgemm_wide;                                      // tools/cmp_sk
 
 // skip (+)= sum_{n = layer0 .. layer0 + nl - 1} (W_skip,n g_n + b_skip,n); gimg = [nl][B][L][256] bf16 (slot n - layer0)
 int launch_skipgemm_bf16(ap_ctx *ctx, int layer0, int nl, const void *gimg, float *skip, int accumulate, int B, int L, hipStream_t st) {
+  BlockPlan p;
+  if (int e = plan_refused(skipgemm_plan(block_ask(ctx, 0, B, L), layer0, nl, &p), p)) return e;
   const int C = ctx->C, S = ctx->S;
-  if (C != 256 || S != 256 || !ctx->w2p_bf) { set_error("skip GEMM: AP_PREC_BF16 context with res = skip = 256 channels only"); return -22; }
-  if (nl < 1 || layer0 < 0 || layer0 + nl > ctx->NL || B < 1 || L < 1) { set_error("skip GEMM: layers [%d, %d) B=%d L=%d", layer0, layer0 + nl, B, L); return -22; }
-  // (1024 L: a clip's fp32 skip rows -- the out-of-clip sentinel offset 0x80000000 of the epilogue must lie beyond them)
-  if ((size_t)L * 1024 >= ((size_t)1 << 31)) { set_error("skip GEMM: clip too long (L * 1024 bytes of skip rows per clip must stay below 2^31)"); return -22; }
-  const int n_cu = device_cu_count();
-  const int ntiles = (L + SPT - 1) / SPT;
-  const int nblk = B * ntiles;
-  const int grid = nblk < n_cu ? nblk : n_cu;
   const size_t n2 = (size_t)(C + S) * C;
-  const unsigned wbytes = (unsigned)((size_t)ctx->NL * n2 * 2);
-  const unsigned w2_off = (unsigned)((size_t)layer0 * n2 * 2);
+  const unsigned wbytes = (unsigned)((size_t)ctx->NL * n2 * 2), w2_off = (unsigned)((size_t)layer0 * n2 * 2);
   const float *b2 = ctx->b2 + (size_t)layer0 * (C + S) + C;
 #ifdef AP_TOOLS
   if (g_skipgemm_wide == 1) return launch_skipgemm_bf16w(ctx, layer0, nl, gimg, skip, accumulate, B, L, st);
 #endif
-  if (L % 4)
-    skipgemm_bf16_kernel<true><<<(unsigned)grid, 512, 0, st>>>(gimg, skip, ctx->w2p_bf, wbytes, w2_off, (unsigned)(n2 * 2), b2, (unsigned)(C + S), B, L, nl,
-                                                             accumulate, ntiles, nblk);
-  else
-    skipgemm_bf16_kernel<false><<<(unsigned)grid, 512, 0, st>>>(gimg, skip, ctx->w2p_bf, wbytes, w2_off, (unsigned)(n2 * 2), b2, (unsigned)(C + S), B, L, nl,
-                                                              accumulate, ntiles, nblk);
+  auto go = [&](auto *kernel) {
+    kernel<<<p.grid, p.wg, 0, st>>>(gimg, skip, ctx->w2p_bf, wbytes, w2_off, (unsigned)(n2 * 2), b2, (unsigned)(C + S), B, L, nl, accumulate, p.ntiles,
+                                    (int)p.nblk);
+  };
+  if (p.rag) go(skipgemm_bf16_kernel<true>);
+  else go(skipgemm_bf16_kernel<false>);
   AP_HIP(hipGetLastError());
   return 0;
 }

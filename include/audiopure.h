@@ -193,8 +193,8 @@ int ap_resblock_fwd(ap_ctx *ctx, int layer, const float *h_in, const float *part
  *                         by G x B x L x C x 2 bytes: ap_workspace_bytes follows); 0 (default) = the fused block per layer.
  * Results: h identical bit for bit; skip differs from the per-layer form by fp32 summation order only (the bf16 products are
  * the same; a group's K = G x 256 is accumulated in the matrix pipe's fp32 accumulators).
- * ap_resblock_fwd_gate launches of at most one 128-sample tile per CU (one or two 1 s clips) run on 64-sample tiles
- * (ap_resblock_bf16s.hip) with bit-identical results: a clip's h' and g image do not depend on the batch it travels in.
+ * ap_resblock_fwd_gate launches of at most 256 128-sample tiles -- one per CU of the MI355X; one or two 1 s clips -- run on 64-sample
+ * tiles (ap_resblock_bf16s.hip; the rule: block_plan, csrc/ap_block_plan.h) with bit-identical results: a clip's h' and g image do not depend on the batch it travels in.
  * ap_resblock_fwd_gate: AP_PREC_BF16 only.  ap_skip_gemm and ap_ctx_set_skip_group(G > 0): AP_PREC_BF16 and AP_PREC_BF16_STORE,
  * res = skip = 256 channels; -22 in every other mode (ap_ctx_set_skip_group(0) is accepted everywhere). */
 int ap_resblock_fwd_gate(ap_ctx *ctx, int layer, const float *h_in, const float *part_t_layer, float *h_out,
@@ -213,8 +213,8 @@ int ap_ctx_set_skip_group(ap_ctx *ctx, int layers_per_group);
  * ap_resblock_fwd / _gate / _save return -22 in this mode (their h tensors are fp32; ap_resblock_bwd_bf16 recomputes from an fp32
  * layer input this mode never forms: use ap_resblock_fwd_u_save + ap_resblock_bwd_bf16_saved).
  * ap_eps_fwd / ap_purify_* run the whole sweep.  ap_init_conv_u, ap_resblock_fwd_u and ap_resblock_fwd_u_save return -22 in every other
- * mode and width.  ap_resblock_fwd_u launches of at most one 128-sample tile per CU run on 64-sample tiles (ap_resblock_bf16us.hip)
- * with bit-identical results, as ap_resblock_fwd_gate's do. */
+ * mode and width.  ap_resblock_fwd_u launches of at most 256 128-sample tiles run on 64-sample tiles (ap_resblock_bf16us.hip) with
+ * bit-identical results, as ap_resblock_fwd_gate's do (block_plan, csrc/ap_block_plan.h). */
 int ap_init_conv_u(ap_ctx *ctx, const float *x, const float *part_t_layer0, void *u_out, int B, int L, void *stream);
 int ap_resblock_fwd_u(ap_ctx *ctx, int layer, const void *u_in, const float *part_t_next, void *u_out, void *g_image, int B, int L,
                       void *stream);

@@ -586,32 +586,17 @@ int g_ablate_bf16 = 0;
 unsigned long long *g_trace_bf16 = nullptr;   // ap_debug_trace: device buffer of nblk x 2 x 16 timestamps, or null
 #endif
 
-int launch_resblock_bf16(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
-                         int accumulate, int B, int L, hipStream_t st, void *gout, void *fout) {
+int launch_resblock_bf16w(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
+                          int accumulate, int B, int L, hipStream_t st);   // ap_resblock_bf16w.hip: one wave per SIMD; 1 if the shape is not served
+// Tried before the plan's kernel for a fused AP_PREC_BF16 launch (launch_resblock): 1 = no switch asks for a kernel of tools/csrc, or
+// the one asked for does not serve the shape -- the planned persistent kernel (ap_resblock_bf16p.hip) takes the launch.
+// ap_debug_bf16_dbg bit 0x1000 or a trace buffer: this file's per-tile kernel (any d, any L); bit 0x20000: the one-wave-per-SIMD
+// experiment (ap_resblock_bf16w.hip; bit-identical, 20 % slower: DESIGN.md 3.4) -- tools/ab_bf16w.py, ablate_bf16w.py, trace_resblock_bf16w.py
+int try_resblock_bf16_tools(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip,
+                            int accumulate, int B, int L, hipStream_t st) {
   const int C = ctx->C, S = ctx->S;
-  if (gout) return launch_resblock_bf16p(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st, gout, fout);
-  if (C != 256) {
-    set_error("AP_PREC_BF16 is built for res_channels = 256 only (got %d)", C);
-    return -22;
-  }
-  // dispatch: the persistent kernel (ap_resblock_bf16p.hip) where it serves the shape, else this file's per-tile kernel
-  // (any d, any L).  Tools builds can force the per-tile kernel for A/B timing (ap_debug_bf16_dbg bit 0x1000).
-#ifdef AP_TOOLS
-  const bool force_tile = (g_dbg_bf16 & 0x1000) != 0;
-  if (!force_tile && !g_trace_bf16)
-#endif
-  {
-#ifdef AP_TOOLS
-    // tools builds only: the one-wave-per-SIMD experiment (ap_resblock_bf16w.hip; bit-identical, 20 % slower: DESIGN.md 3.4)
-    // serves the launch when bit 0x20000 asks for it -- tools/ab_bf16w.py, ablate_bf16w.py, trace_resblock_bf16w.py
-    if (g_dbg_bf16 & 0x20000) {
-      const int rcw = launch_resblock_bf16w(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
-      if (rcw != 1) return rcw;                                  // 1: shape not served there -> the eight-wave persistent kernel
-    }
-#endif
-    const int rc = launch_resblock_bf16p(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st);
-    if (rc != 1) return rc;                                      // 1: shape not served there (L % 4, C, S) -> per-tile kernel
-  }
+  if (!(g_dbg_bf16 & 0x1000) && !g_trace_bf16)
+    return (g_dbg_bf16 & 0x20000) ? launch_resblock_bf16w(ctx, layer, hin, pt, hout, skip, accumulate, B, L, st) : 1;
   const int d = 1 << (layer % ctx->cfg.dilation_cycle);
   const int ntiles = (L + BT - 1) / BT;
   const int nblk = B * ntiles;

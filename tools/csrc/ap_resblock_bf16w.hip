@@ -32,7 +32,7 @@ namespace ap {
 
 namespace {
 
-constexpr int PT_ = 128;                 // time tile
+constexpr int PT_ = BLOCK_PT;            // time tile
 constexpr int KC_ = 32;                  // channels per staged chunk -> 96 K rows = 6 k-steps of 16
 constexpr int PS_ = 32;                  // fp32 per row of the wave-private output patch (128 B)
 

@@ -38,7 +38,7 @@ namespace ap {
 namespace {
 
 constexpr int WC_ = 256;                 // res = skip channels
-constexpr int NP_ = 32;                  // pairs per tile
+constexpr int NP_ = BLOCK_NP;            // pairs per tile
 constexpr int KCW_ = 32;                 // channels per staged chunk
 constexpr int NCH_ = WC_ / KCW_;         // 8 chunks
 constexpr int XS_ = KCW_ + 4;            // floats per (product, column) row of the X image
@@ -502,7 +502,7 @@ static constexpr int g_no_q16 = 0;
 // returns 1 if the shape is not served (caller: the direct-form kernel)
 int launch_resblock_f32w_parent(ap_ctx *ctx, int layer, const float *hin, const float *pt, float *hout, float *skip, int accumulate,
                          int B, int L, hipStream_t st, float *aout) {
-  if (!resblock_f32w_serves(ctx, B, L)) return 1;
+  if (!block_f32w_serves(block_ask(ctx, layer, B, L))) return 1;
   const int g_ncu = device_cu_count();
   const int logd = layer % ctx->cfg.dilation_cycle;
   const long long d = 1ll << logd;

@@ -10,7 +10,7 @@ namespace ap {
 
 namespace {
 
-constexpr int SPT = 128;                  // time tile
+constexpr int SPT = BLOCK_SPT;            // time tile
 constexpr int SGS = 256 + 8;              // bf16 per column row of the g image in LDS (528 B)
 constexpr int SPS = 32;                   // fp32 per row of the wave-private output patch (128 B)
 
