@@ -194,6 +194,10 @@ SIGNATURES = {
     "ap_mixup_rows": (_i, [_fp, _vp, _fp, _fp, _i, _i, _vp]),
     "ap_mixup_targets": (_i, [_vp, _vp, _fp, _fp, _i, _i, _vp]),
     "ap_scale_by_scalar": (_i, [_fp, _fp, _f, _fp, _sz, _vp]),
+    "ap_aug_wave": (_i, [_fp, _vp, _fp, _vp, _vp, _vp, _fp, _i, _i, _i, _vp]),
+    "ap_stft": (_i, [_fp, _fp, _i, _i, _i, _vp]),
+    "ap_phase_vocoder_shift": (_i, [_fp, _fp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "ap_mel_from_stft": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _vp]),
 }
 
 _LIB = None

@@ -6,14 +6,9 @@
 
 #include "ap_common.h"
 #include "ap_fft.h"
+#include "ap_mel.h"
 
 namespace ap {
-
-constexpr int NFFT = 2048, HOP = 512, NBIN = NFFT / 2 + 1, MAX_MELS = 128;
-
-struct MelPts {
-  float f[MAX_MELS + 2];   // filter corner frequencies in Hz (n_mels + 2 used)
-};
 
 __global__ __launch_bounds__(256) void melspec_kernel(const float *__restrict__ x, float *__restrict__ out, MelPts pts,
                                                       int n_mels, int n_frames, int L) {
@@ -43,19 +38,7 @@ __global__ __launch_bounds__(256) void melspec_kernel(const float *__restrict__ 
   }
   __syncthreads();
   if (tid < n_mels) {
-    const float f0 = pts.f[tid], f1 = pts.f[tid + 1], f2 = pts.f[tid + 2];
-    const float binhz = 8000.0f / (float)(NBIN - 1);   // all_freqs = linspace(0, sr/2, n_freqs)
-    int lo = (int)floorf(f0 / binhz), hi = (int)ceilf(f2 / binhz);
-    lo = max(lo, 0);
-    hi = min(hi, NBIN - 1);
-    const float enorm = 2.0f / (f2 - f0);              // slaney area normalisation
-    const float id = 1.0f / (f1 - f0), iu = 1.0f / (f2 - f1);
-    float s = 0.f;
-    for (int k = lo; k <= hi; k++) {
-      const float fr = (float)k * binhz;
-      const float w = fmaxf(0.f, fminf((fr - f0) * id, (f2 - fr) * iu));
-      s = __builtin_fmaf(w * enorm, pw[k], s);
-    }
+    const float s = mel_filter_power(pts, pw, tid);
     out[((size_t)b * n_mels + tid) * n_frames + frame] = 10.0f * log10f(fmaxf(s, 1e-10f));   // AmplitudeToDB('power')
   }
 }
@@ -169,6 +152,13 @@ static double mel_to_hz_slaney(double m) {
   return m >= min_log_mel ? min_log_hz * exp(logstep * (m - min_log_mel)) : f_sp * m;
 }
 
+void slaney_mel_points(MelPts *pts, int n_mels) {
+  const double m0 = hz_to_mel_slaney(0.0), m1 = hz_to_mel_slaney(8000.0);
+  for (int i = 0; i < n_mels + 2; i++) pts->f[i] = (float)mel_to_hz_slaney(m0 + (m1 - m0) * i / (n_mels + 1));
+}
+
+void launch_mel_refmax(float *out, int rows, int n, hipStream_t st) { mel_refmax_kernel<<<rows, 256, 0, st>>>(out, n); }
+
 }  // namespace ap
 
 extern "C" int ap_melspec_db_bwd(const float *x, const float *dout, float *dx, float *scratch, int n_mels, int B, int L,
@@ -177,8 +167,7 @@ extern "C" int ap_melspec_db_bwd(const float *x, const float *dout, float *dx, f
   if (!x || !dout || !dx || !scratch || B < 1 || L < 1) { set_error("ap_melspec_db_bwd: bad argument"); return -22; }
   if (n_mels < 1 || n_mels > MAX_MELS) { set_error("ap_melspec_db_bwd: n_mels %d outside [1, %d]", n_mels, MAX_MELS); return -22; }
   MelPts pts;
-  const double m0 = hz_to_mel_slaney(0.0), m1 = hz_to_mel_slaney(8000.0);
-  for (int i = 0; i < n_mels + 2; i++) pts.f[i] = (float)mel_to_hz_slaney(m0 + (m1 - m0) * i / (n_mels + 1));
+  slaney_mel_points(&pts, n_mels);
   const int n_frames = 1 + L / HOP;
   hipStream_t st = (hipStream_t)stream;
   melspec_bwd_kernel<<<dim3(n_frames, B), 256, 0, st>>>(x, dout, scratch, pts, n_mels, n_frames, L);
@@ -193,13 +182,12 @@ extern "C" int ap_melspec_db(const float *x, float *out, int n_mels, int mode, i
   if (n_mels < 1 || n_mels > MAX_MELS) { set_error("ap_melspec_db: n_mels %d outside [1, %d]", n_mels, MAX_MELS); return -22; }
   if (mode != 0 && mode != 1) { set_error("ap_melspec_db: mode %d", mode); return -22; }
   MelPts pts;
-  const double m0 = hz_to_mel_slaney(0.0), m1 = hz_to_mel_slaney(8000.0);
-  for (int i = 0; i < n_mels + 2; i++) pts.f[i] = (float)mel_to_hz_slaney(m0 + (m1 - m0) * i / (n_mels + 1));
+  slaney_mel_points(&pts, n_mels);
   const int n_frames = 1 + L / HOP;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(n_frames, B);
   melspec_kernel<<<grid, 256, 0, st>>>(x, out, pts, n_mels, n_frames, L);
-  if (mode == 1) mel_refmax_kernel<<<B, 256, 0, st>>>(out, n_mels * n_frames);
+  if (mode == 1) launch_mel_refmax(out, B, n_mels * n_frames, st);
   AP_HIP(hipGetLastError());
   return 0;
 }

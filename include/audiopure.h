@@ -800,6 +800,35 @@ int ap_mixup_targets(const int64_t *labels, const int64_t *index, const float *w
  * loss without a host read.  out may be x. */
 int ap_scale_by_scalar(const float *x, const float *g, float factor, float *out, size_t n, void *stream);
 
+/* ---- train-time augmentation and mel features of the speech-commands classifiers (train_speech_commands.py:60-68), batched on the
+ * device.  A lane is one clip or one background clip; every random number is drawn on the host and arrives as a per-lane DEVICE array
+ * (int32 / float / double as typed).  fp32 data, complex values as (re, im) float pairs, STFTs laid out [lane][frame][1025 bins].
+ * Nothing allocated, no synchronise, no atomics: two runs give equal bits.  A per-lane value out of range cannot be refused without
+ * a host read; every index derived from one is clamped, so nothing is read or written out of bounds. ---- */
+/* ChangeAmplitude, ChangeSpeedAndPitchAudio, FixAudioLength (transforms/transforms_wav.py:50-78,34-48) in one pass: x [N][L_max] with
+ * len[N] valid samples each -> out [N][L_out],  out[j] = amp * np.interp(j * speed_fac, arange(len), x)  for j < n_interp (the host's
+ * len(np.arange(0, len, speed_fac))), the position formed in fp64, positions in (len-1, len) taking x[len-1]; zeros from n_interp to
+ * L_out, cut at L_out.  speed_applied[lane] == 0: out[j] = amp * x[j] for j < len, one fp32 rounding (speed_fac, n_interp unread). */
+int ap_aug_wave(const float *x, const int32_t *len, const float *amp, const double *speed_fac, const int32_t *n_interp,
+                const int32_t *speed_applied, float *out, int N, int L_max, int L_out, void *stream);
+/* ToSTFT (transforms/transforms_stft.py:14-28): librosa.stft(x, n_fft=2048, hop_length=512) -- periodic Hann, center=True, F = 1 + L / 512
+ * frames, complex64 -- of x [N][L] into out [N][F][1025][2].  pad_mode AP_PAD_CONSTANT (librosa >= 0.10; what ap_melspec_db assumes) or
+ * AP_PAD_REFLECT (older librosa; needs L > 1024). */
+#define AP_PAD_CONSTANT 0
+#define AP_PAD_REFLECT 1
+int ap_stft(const float *x, float *out, int pad_mode, int N, int L, void *stream);
+/* StretchAudioOnSTFT, TimeshiftAudioOnSTFT, FixSTFTDimension (transforms/transforms_stft.py:30-68,86-99) fused: D [N][F][1025][2] ->
+ * out, same shape.  stretch_applied[lane] != 0: S = librosa.core.phase_vocoder(D, rate, hop_length=512) with n_out =
+ * len(np.arange(0, F, rate)) columns from the host, the step positions t * rate formed in fp64, the phase accumulator kept wrapped to
+ * [-pi, pi] and the expected advance pi k / 2 applied as k mod 4 quarter turns; == 0: S = D (rate, n_out unread), copied bit for bit.
+ * out[:, c] = S[:, c + shift] where c and c + shift are both columns of S, zeros elsewhere.  F <= 4096; out must not alias D. */
+int ap_phase_vocoder_shift(const float *D, float *out, const double *rate, const int32_t *n_out, const int32_t *stretch_applied,
+                           const int32_t *shift, int N, int F, void *stream);
+/* AddBackgroundNoiseOnSTFT, ToMelSpectrogramFromSTFT (transforms/transforms_stft.py:70-84,101-114): for clip b < B of the N lanes of
+ * D [N][F][1025][2]:  D[b] (1 - p[b]) + D[noise_lane[b]] p[b]  (noise_lane[b] outside [0, N): D[b] as it is), |.|^2, librosa.filters.mel
+ * (sr=16000, n_fft=2048, n_mels) as ap_melspec_db builds it, librosa.power_to_db(ref=np.max) -> out [B][n_mels][F]. */
+int ap_mel_from_stft(const float *D, const int32_t *noise_lane, const float *p, float *out, int n_mels, int B, int N, int F, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
