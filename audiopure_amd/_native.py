@@ -198,6 +198,11 @@ SIGNATURES = {
     "ap_stft": (_i, [_fp, _fp, _i, _i, _i, _vp]),
     "ap_phase_vocoder_shift": (_i, [_fp, _fp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "ap_mel_from_stft": (_i, [_fp, _vp, _fp, _fp, _i, _i, _i, _i, _vp]),
+    "ap_pgd_chunk": (_i, []),
+    "ap_pgd_init": (_i, [_fp, _fp, _fp, _fp, _f, _i, _i, _vp]),
+    "ap_pgd_step_linf": (_i, [_fp] * 5 + [_vp, _vp, _fp, _i, _vp, _f, _fp, _f, _i, _i, _i, _i, _vp]),
+    "ap_pgd_l2_workspace_bytes": (_sz, [_i, _i]),
+    "ap_pgd_step_l2": (_i, [_fp] * 5 + [_vp, _vp, _fp, _i, _vp, _f, _fp, _f, _i, _i, _vp, _sz, _i, _i, _vp]),
 }
 
 _LIB = None

@@ -9,12 +9,17 @@ re-exported unchanged -- ``stage_1`` (PGD), ``stage_2``, ``generate``, EOT, ``pr
 * ``PsychoacousticMasker`` is ``audiopure_amd.robustness_eval.psychoacoustic.PsychoacousticMasker`` (no librosa);
 * ``AudioAttack`` is a subclass that overrides only ``_stabilized_threshold_and_psd_maximum`` and
   ``_loss_gradient_masking_threshold`` (same signatures, shapes and return types), which run on the HIP kernels instead of
-  host numpy and ``torch.stft``.
+  host numpy and ``torch.stft``;
+* ``NativeStage1AudioAttack`` is added: ``AudioAttack`` whose ``stage_1`` (PGD), for a float32 device batch [B, 1, L] under the linf
+  norm, keeps the checkout's model, EOT and criterion calls and runs the per-sample loops, the update, the projection and the final
+  gather on ``ap_pgd_step_linf`` (``audiopure_amd.attacks.stage_1``): one host read after the loop, the checkout's bits.  Everything
+  else -- l2, 16-bit data, CPU tensors -- calls the checkout's method.  ``AudioAttack.stage_1`` itself stays the checkout's.
 """
 import importlib.util
 import os
 import sys
 
+from audiopure_amd import attacks as _attacks
 from audiopure_amd.robustness_eval import psychoacoustic as _psy
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,3 +63,12 @@ class AudioAttack(_ref.AudioAttack):
     def _loss_gradient_masking_threshold(self, perturbation, x, masking_threshold_stabilized, psd_maximum_stabilized):
         return _psy.masking_threshold_loss_and_grad(perturbation, masking_threshold_stabilized, psd_maximum_stabilized,
                                                     hop_size=self.masker.hop_size)
+
+
+class NativeStage1AudioAttack(AudioAttack):
+    """``AudioAttack`` with stage 1's loop bookkeeping on the device too, where ``audiopure_amd.attacks.stage_1`` serves the call."""
+
+    def stage_1(self, x, y):
+        if _attacks.stage_1_served(self, x, y):
+            return _attacks.stage_1(self, x, y)
+        return super().stage_1(x, y)

@@ -829,6 +829,46 @@ int ap_phase_vocoder_shift(const float *D, float *out, const double *rate, const
  * (sr=16000, n_fft=2048, n_mels) as ap_melspec_db builds it, librosa.power_to_db(ref=np.max) -> out [B][n_mels][F]. */
 int ap_mel_from_stft(const float *D, const int32_t *noise_lane, const float *p, float *out, int n_mels, int B, int N, int F, void *stream);
 
+/* ---- PGD attack loop (ap_attack.hip): what the reference's adversarial-training scripts run between two model calls of `pgd`
+ * (audio_models/RCNN_KWS/train.py:84-121, audio_models/ConvNets_SpeechCommands/adv_train_speech_commands.py:139-183) and what stage 1
+ * of the white-box attack runs (robustness_eval/white_box_attack.py:362-471).  The loop has no early exit, so with these it is enqueued
+ * without a host read.  Rows are [B][n] fp32 ([B,1,L] waveforms); x, u, g, delta, x_pert and x_adv share the layout and a row may
+ * start at any 4-byte offset (16-byte accesses where every row base allows).  Streaming kernels, one chunk of ap_pgd_chunk() elements
+ * of a row per workgroup.  torch's fp32 rounding sequence, one rounding per operator and never an fma: the bits of the scripts' loops.
+ * Nothing allocated, no synchronise, no atomics: two runs give equal bits.  Every refusal is -22 with ap_last_error set before any
+ * launch.  1 <= B <= 65535, n >= 1; no output may overlap another tensor of the call. ---- */
+int ap_pgd_chunk(void);
+/* The random start (adv_train_speech_commands.py:146-148, RCNN_KWS/train.py:91-93), u the uniform draws of torch.rand_like:
+ *   d = fl(eps fl(fl(2u) - 1)),  delta = fl(clamp(fl(x + d), -1, 1) - x),  x_pert = fl(x + delta)
+ * u == NULL: stage 1's zero start (white_box_attack.py:378,384): delta = 0, x_pert = fl(x + 0).  One launch. */
+int ap_pgd_init(const float *x, const float *u, float *delta, float *x_pert, float eps, int B, int n, void *stream);
+/* One iteration's bookkeeping and linf update in ONE launch (adv_train_speech_commands.py:158-169, RCNN_KWS/train.py:103-113,
+ * white_box_attack.py:399-407,442-453).  g is the gradient of the loss at x_pert.  The row's prediction is pred[b] (int64), or, with
+ * pred NULL, the argmax of scores[b][0..K) taken by the kernel: the LOWEST index of the row maximum, a NaN counting as the maximum (as
+ * Tensor.max does); exactly one of pred and scores is given, 1 <= K <= 4096.  For row b:
+ *   hit = targeted ? pred == y[b] : pred != y[b];   hit: x_adv[b] = x_pert[b] (the iterate BEFORE the update) and found[b] = 1 --
+ *         a later hit overwrites an earlier one, as the scripts' loops do
+ *   last != 0: rows with found[b] == 0 get x_adv[b] = x_pert[b] (the fallback of :177-179 / :461-465); nothing else is written and g
+ *         may be NULL
+ *   otherwise: d = clamp(fl(delta + step sgn(g)), -eps_b, eps_b),  delta = fl(clamp(fl(x + d), -1, 1) - x),  x_pert = fl(x + delta)
+ * step is signed: +alpha untargeted, -lr targeted.  sgn is torch.sign -- (0 < g) - (g < 0): +-0 and NaN give 0; clamp passes a NaN
+ * on.  eps_b = eps_rows[b] (stage 1 keeps a bound per sample), or eps with eps_rows NULL.  found is uint8 [B], zeroed by the caller
+ * before the first iteration. */
+int ap_pgd_step_linf(const float *x, const float *g, float *delta, float *x_pert, float *x_adv, uint8_t *found, const int64_t *pred,
+                     const float *scores, int K, const int64_t *y, float step, const float *eps_rows, float eps, int targeted, int last,
+                     int B, int n, void *stream);
+/* The same iteration with the l2 rule of adv_train_speech_commands.py:171 (project_to_norm_ball, :112-123), norms per row:
+ *   g^ = g min(1, 1 / |g|_b),  v = delta + step g^,  d = v min(1, eps_b / |v|_b),  then the box step as above
+ * THREE launches (one with last != 0): the squares of g summed per chunk, the squares of v per chunk (it adds the first launch's
+ * partials of its row), the update (it adds both).  The partials are fp64 and are added in index order, the norm is rounded to fp32 as
+ * torch.norm's is; the result is held to the float64 expression (measured: the same error as float32 torch's), not to torch's bits.  A row of zeros
+ * behaves as torch's: 1 / 0 = inf, min(1, inf) = 1, no NaN appears.  workspace: ap_pgd_l2_workspace_bytes(B, n) bytes, 8-byte
+ * aligned (unread with last != 0). */
+size_t ap_pgd_l2_workspace_bytes(int B, int n);
+int ap_pgd_step_l2(const float *x, const float *g, float *delta, float *x_pert, float *x_adv, uint8_t *found, const int64_t *pred,
+                   const float *scores, int K, const int64_t *y, float step, const float *eps_rows, float eps, int targeted, int last,
+                   void *workspace, size_t ws_bytes, int B, int n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
