@@ -83,17 +83,6 @@ __device__ __forceinline__ void update(float x, float g, float &delta, float &xp
   xp = x + delta;
 }
 
-// sum over the workgroup in a fixed order (tree over LDS); every lane returns it
-__device__ __forceinline__ double pgd_block_sum(double s, double *red) {
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = PGD_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // a row's norm from its per-chunk partials, added in index order by every lane alike; rounded to fp32 as torch.norm's result is
 __device__ __forceinline__ float row_norm(const double *part, int chunks) {
   double s = 0.0;
@@ -102,6 +91,7 @@ __device__ __forceinline__ float row_norm(const double *part, int chunks) {
 }
 
 // lowest index of the row maximum of z[0..K), a NaN counting as the maximum (Tensor.max); every lane returns it
+// (not block_tree: the tree carries an index beside the value, with a tie rule)
 __device__ __forceinline__ int row_argmax(const float *z, int K, float *sv, int *si) {
   constexpr int NONE = 0x7fffffff;
   float mv = 0.f;
@@ -250,7 +240,7 @@ __global__ __launch_bounds__(PGD_THREADS) void pgd_sqnorm_kernel(const PgdArgs a
     const float v = SECOND ? l2_proposal(g[i], delta[i], r) : g[i];
     s += (double)v * (double)v;
   }
-  s = pgd_block_sum(s, red);
+  s = block_tree<PGD_THREADS>(s, red, SumOp{});
   if (threadIdx.x == 0) part[(size_t)b * a.chunks + blockIdx.x] = s;
 }
 

@@ -1239,8 +1239,6 @@ extern "C" int ap_pool2d(const float *x, float *y, int BC, int H, int W, int k, 
 // =============================================================================================================
 namespace ap {
 
-__device__ __forceinline__ float silu_f(float x) { return x / (1.0f + expf(-x)); }
-
 // GroupNorm32 (nn.py:17-19,95-102) [+ (1 + scale) * . + shift of use_scale_shift_norm (unet.py:184-190)] [+ SiLU].
 // One workgroup per (sample, group); two passes (mean, then centred variance) like ATen's RowwiseMoments.
 __global__ __launch_bounds__(256) void groupnorm_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
@@ -1253,31 +1251,19 @@ __global__ __launch_bounds__(256) void groupnorm_kernel(const float *__restrict_
   float *yp = y + ((size_t)b * C + (size_t)g * cpg) * HW;
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += xp[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const float mean = red[0] / (float)n;
+  const float mean = block_tree<256>(s, red, SumOp{}) / (float)n;
   __syncthreads();
   float v = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
     const float dlt = xp[i] - mean;
     v = __builtin_fmaf(dlt, dlt, v);
   }
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const float rstd = 1.0f / sqrtf(red[0] / (float)n + eps);
+  const float rstd = 1.0f / sqrtf(block_tree<256>(v, red, SumOp{}) / (float)n + eps);
   for (int i = threadIdx.x; i < n; i += 256) {
     const int c = g * cpg + i / HW;
     float o = (xp[i] - mean) * rstd * gamma[c] + beta[c];
     if (ss) o = o * (1.0f + ss[(size_t)b * 2 * C + c]) + ss[(size_t)b * 2 * C + C + c];
-    if (act == 2) o = silu_f(o);
+    if (act == 2) o = silu(o);
     else if (act == 1) o = fmaxf(o, 0.f);
     yp[i] = o;
   }
@@ -1309,8 +1295,7 @@ __global__ __launch_bounds__(256) void groupnorm_reg_kernel(const float *__restr
     }
   }
   auto total = [&](float a, int slot) -> float {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    a = wave_sum(a);
     if (T == 64) return a;
     if ((threadIdx.x & 63) == 0) red[slot * 4 + (threadIdx.x >> 6)] = a;
     __syncthreads();
@@ -1342,7 +1327,7 @@ __global__ __launch_bounds__(256) void groupnorm_reg_kernel(const float *__restr
 #pragma unroll
       for (int e = 0; e < 4; e++) {
         float r = __builtin_fmaf(v[u][e], ga, be);
-        if (act == 2) r = silu_f(r);
+        if (act == 2) r = silu(r);
         else if (act == 1) r = fmaxf(r, 0.f);
         o[e] = r;
       }
@@ -1364,7 +1349,7 @@ __global__ void timestep_embedding_kernel(const float *__restrict__ t, const flo
 
 __global__ void silu_kernel(const float *__restrict__ x, float *__restrict__ y, size_t n) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) y[i] = silu_f(x[i]);
+  if (i < n) y[i] = silu(x[i]);
 }
 
 // F.interpolate(scale_factor=2, mode="nearest") (unet.py:60-72)

@@ -18,7 +18,7 @@ namespace {
 // over the whole batch: a chunk of CW_KC positions may start in one image and end in the next (H = W = 1, nn.Linear, contracts over
 // B alone).  The structure and the LDS fragment layout are wgrad_corr_kernel's (ap_wgrad.hip): both operands staged as
 // [row][position] with an ODD row stride, so the 32 lanes of a fragment read hit 32 banks; the next chunk is fetched into
-// registers while this one multiplies; slice z takes a contiguous run of chunks and writes raw partial sums, conv2d_wgrad_reduce
+// registers while this one multiplies; slice z takes a contiguous run of chunks and writes raw partial sums, slice_sum_kernel
 // adds the slices in slice order.  Wave (wm, wn) of the 2 x 2 owns rows [64 wm, +64) x columns [32 wn, +32) of the 128 x 64 tile.
 // A tile lies inside ONE group: rows past Cout/g and columns past (Cin/g) k k are zeros in LDS and are not stored.
 // dy is staged with 16-byte loads where OH OW % 4 == 0 and the pointer allows (a quad then never leaves its image); x likewise for
@@ -192,16 +192,6 @@ __global__ __launch_bounds__(CW_NT) void conv2d_wgrad_kernel(ConvWgradArgs a) {
   }
 }
 
-// dW (+)= slice 0 + slice 1 + ..., in slice order (fp64: the slices' own sums are the matrix pipe's fp32, their sum is rounded once)
-__global__ void conv2d_wgrad_reduce_kernel(const float *__restrict__ part, float *__restrict__ dW, size_t total, int slices, int accumulate) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  double s = 0.0;
-  for (int z = 0; z < slices; z++) s += (double)part[(size_t)z * total + idx];
-  const float v = (float)s;
-  dW[idx] = accumulate ? dW[idx] + v : v;
-}
-
 // 0, or -22 with the error text set: everything ap_conv2d_wgrad refuses, and the geometry it runs on
 int conv_wgrad_plan(int B, int Cin, int H, int W, int Cout, int kh, int kw, int stride, int pad, int groups, int x_cstride, int x_coff,
                     ConvWgradArgs *a) {
@@ -253,26 +243,11 @@ __global__ void conv_flip_kernel(const float *__restrict__ w, float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// BatchNorm2d with batch statistics (nn.BatchNorm2d in training mode; the M5 rule of ap_m5_train.hip): per channel the n = B HW values
-// are cut into BN_SLICES contiguous runs, each summed in fp64 by one workgroup in a fixed order, the slices added in slice order.
-// The variance comes from fp64 sums of fp32 values, so sum x^2 - n mean^2 cancels nothing an fp32 result can see.
+// BatchNorm2d with batch statistics (nn.BatchNorm2d in training mode): per channel the n = B HW values are cut into BN_SLICES
+// contiguous runs, each summed in fp64 by one workgroup in a fixed order (block_wave_sum2), the slices added in slice order by the
+// finalisers M5 shares (bn_stats_final_kernel, bn_bstats_final_kernel: ap_reduce.h).
 // ---------------------------------------------------------------------------------------------
 constexpr int BN_SLICES = 64;
-
-__device__ __forceinline__ void bn_block_sum2(double &a, double &b) {   // valid in thread 0
-  __shared__ double sm[8];
-  for (int d = 32; d; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    b += __shfl_down(b, d, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[2 * w] = a; sm[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = sm[0]; b = sm[1];
-    for (int i = 1; i < 4; i++) { a += sm[2 * i]; b += sm[2 * i + 1]; }
-  }
-}
 
 struct BnArgs {
   const float *x, *y, *dy, *gamma, *beta, *stat_in;
@@ -283,7 +258,8 @@ struct BnArgs {
   float eps, momentum;
 };
 
-// part[slice][c] = (sum x, sum x^2).  grid (C, BN_SLICES)
+// part[slice][c] = (sum x, sum x^2).  grid (C, BN_SLICES).  Not m5t_stats_kernel: a slice here is a contiguous run of the n values, M5's
+// is the clips slice, slice + 64, ... -- two orders, two sets of bits (the same holds for bn2d_bstats_kernel and m5t_bstats_kernel)
 __global__ __launch_bounds__(256) void bn2d_stats_kernel(BnArgs a) {
   const int c = blockIdx.x, sl = blockIdx.y;
   const long long e0 = a.n * sl / BN_SLICES, e1 = a.n * (sl + 1) / BN_SLICES;
@@ -295,30 +271,11 @@ __global__ __launch_bounds__(256) void bn2d_stats_kernel(BnArgs a) {
     s1 += v;
     s2 += v * v;
   }
-  bn_block_sum2(s1, s2);
+  block_wave_sum2(s1, s2);
   if (threadIdx.x == 0) {
     a.part[((size_t)sl * a.C + c) * 2] = s1;
     a.part[((size_t)sl * a.C + c) * 2 + 1] = s2;
   }
-}
-
-// stat = [mean[C]; 1 / sqrt(biased var + eps)[C]]; running = (1 - m) old + m batch, the variance UNBIASED, n / (n - 1)
-__global__ void bn2d_stats_final_kernel(BnArgs a) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= a.C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int sl = 0; sl < BN_SLICES; sl++) {
-    s1 += a.part[((size_t)sl * a.C + c) * 2];
-    s2 += a.part[((size_t)sl * a.C + c) * 2 + 1];
-  }
-  const double n = (double)a.n, mu = s1 / n;
-  double var = s2 / n - mu * mu;
-  if (var < 0.0) var = 0.0;
-  a.stat[c] = (float)mu;
-  a.stat[a.C + c] = (float)(1.0 / sqrt(var + (double)a.eps));
-  const double m = (double)a.momentum;
-  a.rm[c] = (float)((1.0 - m) * (double)a.rm[c] + m * mu);
-  a.rv[c] = (float)((1.0 - m) * (double)a.rv[c] + m * var * (n / (n - 1.0)));
 }
 
 // y = gamma (x - mean) rstd + beta, optional ReLU: the affine first, so gamma of either sign (or 0) is served
@@ -351,26 +308,11 @@ __global__ __launch_bounds__(256) void bn2d_bstats_kernel(BnArgs a) {
     s1 += (double)g;
     s2 += (double)g * (double)xh;
   }
-  bn_block_sum2(s1, s2);
+  block_wave_sum2(s1, s2);
   if (threadIdx.x == 0) {
     a.part[((size_t)sl * a.C + c) * 2] = s1;
     a.part[((size_t)sl * a.C + c) * 2 + 1] = s2;
   }
-}
-
-// d beta = sum dy', d gamma = sum dy' xhat; mean2[c] = their means over the n positions
-__global__ void bn2d_bstats_final_kernel(BnArgs a) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= a.C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int sl = 0; sl < BN_SLICES; sl++) {
-    s1 += a.part[((size_t)sl * a.C + c) * 2];
-    s2 += a.part[((size_t)sl * a.C + c) * 2 + 1];
-  }
-  if (a.dbeta) a.dbeta[c] = (float)s1;
-  if (a.dgamma) a.dgamma[c] = (float)s2;
-  a.mean2[2 * c] = s1 / (double)a.n;
-  a.mean2[2 * c + 1] = s2 / (double)a.n;
 }
 
 // dx = gamma rstd (dy' - mean(dy') - xhat mean(dy' xhat))
@@ -436,7 +378,7 @@ extern "C" int ap_conv2d_wgrad(const float *dy, const float *x, float *dW, void 
   else if (vecp) conv2d_wgrad_kernel<true, false><<<grid, CW_NT, 0, st>>>(a);
   else if (vecq) conv2d_wgrad_kernel<false, true><<<grid, CW_NT, 0, st>>>(a);
   else conv2d_wgrad_kernel<false, false><<<grid, CW_NT, 0, st>>>(a);
-  conv2d_wgrad_reduce_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a.part, dW, total, a.slices, accumulate);
+  slice_sum_kernel<float><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a.part, dW, total, a.slices, 1, 1.0f, accumulate);
   AP_HIP(hipGetLastError());
   return 0;
 }
@@ -476,7 +418,7 @@ extern "C" int ap_bn2d_train_fwd(const float *x, const float *gamma, const float
   const hipStream_t st = (hipStream_t)stream;
   const size_t total = (size_t)B * C * HW;
   bn2d_stats_kernel<<<dim3(C, BN_SLICES), 256, 0, st>>>(a);
-  bn2d_stats_final_kernel<<<(C + 63) / 64, 64, 0, st>>>(a);
+  bn_stats_final_kernel<BN_SLICES><<<(C + 63) / 64, 64, 0, st>>>(a.part, a.rm, a.rv, stat, a.rm, a.rv, C, (double)a.n, eps, momentum);
   bn2d_apply_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a, total);
   AP_HIP(hipGetLastError());
   return 0;
@@ -497,7 +439,7 @@ extern "C" int ap_bn2d_train_bwd(const float *x, const float *y, const float *dy
   const hipStream_t st = (hipStream_t)stream;
   const size_t total = (size_t)B * C * HW;
   bn2d_bstats_kernel<<<dim3(C, BN_SLICES), 256, 0, st>>>(a);
-  bn2d_bstats_final_kernel<<<(C + 63) / 64, 64, 0, st>>>(a);
+  bn_bstats_final_kernel<BN_SLICES><<<(C + 63) / 64, 64, 0, st>>>(a.part, a.mean2, dgamma, dbeta, C, (double)a.n);
   if (dx) bn2d_dx_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a, total);
   AP_HIP(hipGetLastError());
   return 0;

@@ -101,14 +101,14 @@ __global__ __launch_bounds__(256) void median_smooth_bwd_kernel(const float *__r
 }
 
 // ------------------------------------------------------------------------------------------------------------------ AT
-__device__ __forceinline__ float block_sum_1024(float v, float *sh) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+__device__ __forceinline__ float block_sum_1024(float v, float *sh) {   // wave_sum per wave, then over the sixteen waves' sums
+  v = wave_sum(v);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   __syncthreads();                                  // sh may still be read by a previous call
   if (lane == 0) sh[wv] = v;
   __syncthreads();
   v = lane < 16 ? sh[lane] : 0.f;
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum<16>(v);
   return __shfl(v, 0);
 }
 
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(64) void iir_chunk_kernel(const float *__restrict__
     s[i / IIR_CHUNK][i % IIR_CHUNK] = v;
   }
   if (minmax) {
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {                      // (two max butterflies, interleaved: not a sum, left as it is)
       vmax = fmaxf(vmax, __shfl_xor(vmax, o));
       vnmax = fmaxf(vnmax, __shfl_xor(vnmax, o));
     }

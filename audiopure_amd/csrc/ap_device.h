@@ -178,4 +178,35 @@ __device__ __forceinline__ void split3x4(const float (&x)[4], u32x2 (&out)[3]) {
 // the six partial products kept of the nine, as (weight split, activation split)
 #define AP_SPLIT_TERMS(F) F(0, 0) F(0, 1) F(1, 0) F(0, 2) F(2, 0) F(1, 1)
 
+// ---- the non-block kernels' activations and counter-based random numbers -------------------------------------------------------
+__device__ __forceinline__ float sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
+
+// d * act'(y1) for the activation codes of the GroupNorm entry points: 0 none, 1 ReLU, 2 SiLU (silu' = sg (1 + y (1 - sg)))
+__device__ __forceinline__ float act_grad(float d, float y1, int act) {
+  if (act == 2) {
+    const float sg = sigmoid(y1);
+    return d * (sg * (1.0f + y1 * (1.0f - sg)));
+  }
+  if (act == 1) return y1 > 0.f ? d : 0.f;
+  return d;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11): counter (c0..c3), key (k0, k1)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&out)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
 }  // namespace ap
+
+#include "ap_reduce.h"   // the fixed-order sums of the non-block kernels

@@ -20,7 +20,7 @@ __global__ void rownorm_kernel(const float *__restrict__ v, float *__restrict__ 
   const float *p = v + (size_t)row * IK;
   float s = 0.f;
   for (int i = lane; i < IK; i += 64) s = __builtin_fmaf(p[i], p[i], s);
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) norm[row] = sqrtf(s);
 }
 
@@ -138,8 +138,6 @@ int launch_fold_and_pack(ap_ctx *ctx, const float *blob, hipStream_t st) {
 // diffusion-step embedding MLP + every block's fc_t   (util.py:68-93; WaveNet.py:82-83,124-126)
 // The step is shared by the whole batch in every caller (diffwave_ddpm.py:157,169,177).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float swish_acc(float x) { return x / (1.0f + expf(-x)); }
-
 // One workgroup of 8 waves = eight rows of fc_t2 (one per wave).  Every workgroup first recomputes all of fc_t1 into LDS -- 65 k
 // multiply-adds, wave-per-row dot products, sixteen rows per pass and wave -- so there is no second launch, no scratch buffer and no grid
 // barrier.  Every load is UNCONDITIONAL (indices clamped, the product masked): a load inside `if (row < Emid)` sits in its own basic
@@ -169,7 +167,7 @@ __global__ __launch_bounds__(512) void embed_mlp_kernel(const float *__restrict_
 #pragma unroll
       for (int i = 0; i < 16; i++) s[i] = __builtin_fmaf(w1[(size_t)min(o0 + 8 * i, Emid - 1) * Ein + k], ev, s[i]);
     }
-    for (int m = 32; m > 0; m >>= 1) {
+    for (int m = 32; m > 0; m >>= 1) {                           // (wave_sum's order, the sixteen butterflies interleaved step by step)
 #pragma unroll
       for (int i = 0; i < 16; i++) s[i] += __shfl_xor(s[i], m);
     }
@@ -177,7 +175,7 @@ __global__ __launch_bounds__(512) void embed_mlp_kernel(const float *__restrict_
 #pragma unroll
     for (int i = 0; i < 16; i++) mine = lane == i ? s[i] : mine;
     const int o = o0 + 8 * lane;
-    if (lane < 16 && o < Emid) e1[o] = swish_acc(mine + b1[o]);
+    if (lane < 16 && o < Emid) e1[o] = silu(mine + b1[o]);
   }
   __syncthreads();
   const int o2 = min((int)blockIdx.x * 8 + wave, Eout - 1);      // (a wave past the last row recomputes it and does not store)
@@ -189,8 +187,8 @@ __global__ __launch_bounds__(512) void embed_mlp_kernel(const float *__restrict_
 #pragma unroll
     for (int i = 0; i < 8; i++) s = kk + 64 * i + lane < Emid ? __builtin_fmaf(wv[i], e1[kk + 64 * i + lane], s) : s;
   }
-  for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
-  if (lane == 0 && (int)blockIdx.x * 8 + wave < Eout) emb_out[o2] = swish_acc(s + b2[o2]);
+  s = wave_sum(s);
+  if (lane == 0 && (int)blockIdx.x * 8 + wave < Eout) emb_out[o2] = silu(s + b2[o2]);
 }
 
 // part_t[row] = fct_w[row] . emb + fct_b[row]; one wave per row, rows = NL*C
@@ -212,7 +210,7 @@ __global__ void fct_kernel(const float *__restrict__ w, const float *__restrict_
 #pragma unroll
     for (int u = 0; u < 8; u++) s = i0 + 64 * u + lane < E ? __builtin_fmaf(wv[u], ev[u], s) : s;
   }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   if (lane == 0) out[row] = s + b[row];
 }
 
@@ -587,20 +585,6 @@ int launch_resblock(ap_ctx *ctx, int layer, const float *hin, const float *pt, f
 // ---------------------------------------------------------------------------------------------
 // counter-based noise: Philox4x32-10 + Box-Muller, keyed on (seed; quad, draw, global utterance)
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                              uint32_t k1, uint32_t (&out)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __device__ __forceinline__ void philox_normal4(uint64_t seed, uint32_t draw, uint64_t utt, uint32_t quad,
                                                float (&z)[4]) {
   uint32_t r[4];

@@ -44,8 +44,6 @@ static KwsOff kws_layout(int n_mels, int H, int K) {
   return o;
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
 // x [B][n_mels][T] mel-dB -> log-probabilities [B][K]
 __global__ __launch_bounds__(256) void kws_kernel(const float *__restrict__ x, float *__restrict__ logp,
                                                   const float *__restrict__ w, KwsOff o, int n_mels, int H, int K,
@@ -105,8 +103,8 @@ __global__ __launch_bounds__(256) void kws_kernel(const float *__restrict__ x, f
         const int u = i % H, d = i / H;
         const int t = d == 0 ? s_ : T2 - 1 - s_;
         const float *g_i = gi + ((size_t)d * T2 + t) * 3 * H, *g_h = gh + d * 3 * H;
-        const float r = sigmoidf_(g_i[u] + g_h[u]);
-        const float z = sigmoidf_(g_i[H + u] + g_h[H + u]);
+        const float r = sigmoid(g_i[u] + g_h[u]);
+        const float z = sigmoid(g_i[H + u] + g_h[H + u]);
         const float n = tanhf(g_i[2 * H + u] + r * g_h[2 * H + u]);
         const float hn = (1.0f - z) * n + z * hcur[i];
         hcur[i] = hn;
@@ -391,7 +389,7 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
         const int u = i % H, d = i / H;
         const int t = d == 0 ? s_ : T2 - 1 - s_;
         const float *g_i = gi + d * 3 * H, *g_h = gh + d * 3 * H;
-        const float r = sigmoidf_(g_i[u] + g_h[u]), z = sigmoidf_(g_i[H + u] + g_h[H + u]);
+        const float r = sigmoid(g_i[u] + g_h[u]), z = sigmoid(g_i[H + u] + g_h[H + u]);
         const float n = tanhf(g_i[2 * H + u] + r * g_h[2 * H + u]);
         float *gs = G + ((size_t)d * T2 + t) * 5 * H;
         gs[u] = r; gs[H + u] = z; gs[2 * H + u] = n; gs[3 * H + u] = g_h[2 * H + u]; gs[4 * H + u] = hcur[i];
@@ -578,7 +576,7 @@ __global__ __launch_bounds__(256) void kws_bwd_kernel(const float *__restrict__ 
 // ---- parameter gradients of KWSModel (the reference trains it: audio_models/RCNN_KWS/train.py:147-153) ---------------------
 // Phase 2 of ap_kws_train_bwd: contractions of the sweep's saves over the items k = (clip b, step t), k = b T2 + t.  The item axis
 // is cut into KWS_SLICES contiguous slices -- a constant, not the device's CU count: the slicing sets the summation order -- each
-// slice writes a raw partial gradient blob, and kws_train_sum_kernel adds the slices in slice order in fp64, rounded once.  No
+// slice writes a raw partial gradient blob, and slice_sum_kernel adds the slices in slice order in fp64, rounded once.  No
 // atomics: two runs give the same bits.
 constexpr int KWS_SLICES = 16;
 
@@ -690,15 +688,6 @@ __global__ __launch_bounds__(256) void kws_train_small_kernel(const float *__res
     }
   }
   out[dst] = s;
-}
-
-// dparams = slice 0 + slice 1 + ... in fp64, rounded once
-__global__ __launch_bounds__(256) void kws_train_sum_kernel(const float *__restrict__ part, float *__restrict__ out, size_t total) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  double s = 0.0;
-  for (int sl = 0; sl < KWS_SLICES; sl++) s += (double)part[(size_t)sl * total + e];
-  out[e] = (float)s;
 }
 
 }  // namespace ap
@@ -854,7 +843,7 @@ extern "C" int ap_kws_train_bwd(ap_kws *k, const float *mel, const float *dlogpr
   kws_train_small_kernel<<<dim3((nsmall + 255) / 256, KWS_SLICES), 256, 0, st>>>(mel, workspace, part, o, so, k->n, k->n_mels, H, K,
                                                                                   k->groups, B, T, T1, T2);
   AP_HIP(hipGetLastError());
-  kws_train_sum_kernel<<<(unsigned)((k->n + 255) / 256), 256, 0, st>>>(part, dparams, k->n);
+  slice_sum_kernel<float, KWS_SLICES><<<(unsigned)((k->n + 255) / 256), 256, 0, st>>>(part, dparams, k->n, /* slices: the template's */ 0, 1, 1.0f, 0);
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -17,12 +17,6 @@ constexpr int LOSS_ROWS = LOSS_THREADS / LOSS_WAVE;       // rows per workgroup
 constexpr int LOSS_MAX_K = 4096;
 constexpr int LOSS_MAX_B = 65535;
 
-__device__ __forceinline__ float wave_sum(float v) {     // butterfly: every lane ends with the same bits (a + b == b + a)
-#pragma unroll
-  for (int o = LOSS_WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, LOSS_WAVE);
-  return v;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(LOSS_THREADS) void class_loss_rows_kernel(const float *__restrict__ in, const int64_t *__restrict__ labels,
                                                                       const float *__restrict__ soft, float *__restrict__ loss_rows,
@@ -42,7 +36,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void class_loss_rows_kernel(const flo
     if (mi == 0x7fffffff || v > mv) { mv = v; mi = i; }
   }
 #pragma unroll
-  for (int o = LOSS_WAVE / 2; o > 0; o >>= 1) {
+  for (int o = LOSS_WAVE / 2; o > 0; o >>= 1) {            // (not wave_sum: an index travels with the maximum, with a tie rule)
     const float ov = __shfl_xor(mv, o, LOSS_WAVE);
     const int oi = __shfl_xor(mi, o, LOSS_WAVE);
     if (oi != 0x7fffffff && (mi == 0x7fffffff || ov > mv || (ov == mv && oi < mi))) { mv = ov; mi = oi; }

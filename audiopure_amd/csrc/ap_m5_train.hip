@@ -32,7 +32,7 @@ namespace {
 
 struct M5TPlan {
   int ci[4], co[4], k[4], s[4], lin[4], P[4], Q[4];
-  size_t wT[4], z[4], a[4], sel[4], stat[4], part, wpart, dz, da[2], feat, dlogit, total;   // byte offsets into the workspace
+  size_t wT[4], z[4], a[4], sel[4], stat[4], part, mean2, wpart, dz, da[2], feat, dlogit, total;   // byte offsets into the workspace
   size_t bw[4], bb[4], bg[4], bbe[4], brm[4], brv[4], bfw, bfb;                             // float offsets into the state blob
   size_t gw[4], gb[4], gg[4], gbe[4], gfw, gfb;                                             // float offsets into the gradient blob
   size_t rm[4], rv[4];                                                                      // float offsets into new_running
@@ -89,11 +89,12 @@ int m5t_plan(const ap_m5 *m, int B, int L, M5TPlan *pl) {
     pl->z[i] = off; off += up256(nz * sizeof(float));
     pl->a[i] = off; off += up256(na * sizeof(float));
     pl->sel[i] = off; off += up256(na);
-    pl->stat[i] = off; off += up256((size_t)co[i] * 4 * sizeof(float));
+    pl->stat[i] = off; off += up256((size_t)co[i] * 2 * sizeof(float));                 // [mean[co]; rstd[co]]
     if (nz > zmax) zmax = nz;
     if (na > amax) amax = na;
   }
   pl->part = off; off += up256((size_t)M5T_SLICES * 2 * nc * 2 * sizeof(double));
+  pl->mean2 = off; off += up256((size_t)2 * nc * 2 * sizeof(double));                    // the backward's (mean dy, mean dy xhat) of one stage
   pl->wpart = off; off += up256((size_t)M5T_SLICES * nwm * sizeof(float));
   pl->dz = off; off += up256(zmax * sizeof(float));
   pl->da[0] = off; off += up256(amax * sizeof(float));
@@ -107,22 +108,6 @@ int m5t_plan(const ap_m5 *m, int B, int L, M5TPlan *pl) {
 inline unsigned grid_for(size_t total) {
   size_t b = (total + 255) / 256;
   return (unsigned)(b < 1 ? 1 : b > ((size_t)1 << 20) ? ((size_t)1 << 20) : b);
-}
-
-// sum of (a, b) over the 256 threads of the block in a fixed order (wave shuffles, then the four waves in order); valid in thread 0
-__device__ __forceinline__ void block_sum2(double &a, double &b) {
-  __shared__ double sm[8];
-  for (int d = 32; d; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    b += __shfl_down(b, d, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[2 * w] = a; sm[2 * w + 1] = b; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a = sm[0]; b = sm[1];
-    for (int i = 1; i < 4; i++) { a += sm[2 * i]; b += sm[2 * i + 1]; }
-  }
 }
 
 struct M5TPack {
@@ -174,6 +159,8 @@ __global__ __launch_bounds__(256) void m5t_conv_kernel(const float *__restrict__
 }
 
 // part[slice][o] = (sum z, sum z^2) over the clips b = slice, slice + 64, ... and all P positions (T1), in fp64.  grid (co, slices)
+// Not bn2d_stats_kernel (ap_convnet_train.hip): its slice is a contiguous run of the n values, this one's is every 64th clip -- two
+// orders, two sets of bits (the same holds for m5t_bstats_kernel and bn2d_bstats_kernel).  The finalisers are shared (ap_reduce.h).
 __global__ __launch_bounds__(256) void m5t_stats_kernel(const float *__restrict__ z, double *__restrict__ part, int B, int co, int P) {
   const int o = blockIdx.x, sl = blockIdx.y;
   double s1 = 0.0, s2 = 0.0;
@@ -185,33 +172,14 @@ __global__ __launch_bounds__(256) void m5t_stats_kernel(const float *__restrict_
       s2 += v * v;
     }
   }
-  block_sum2(s1, s2);
+  block_wave_sum2(s1, s2);
   if (threadIdx.x == 0) {
     part[((size_t)sl * co + o) * 2] = s1;
     part[((size_t)sl * co + o) * 2 + 1] = s2;
   }
 }
 
-// stat[o] = (mean, 1 / sqrt(biased var + eps), ., .); the new running statistics as torch forms them: the variance UNBIASED (T4)
-__global__ void m5t_stats_final_kernel(const double *__restrict__ part, const float *__restrict__ rm, const float *__restrict__ rv,
-                                       float *__restrict__ stat, float *__restrict__ new_rm, float *__restrict__ new_rv, int co,
-                                       double n, float eps, float momentum) {
-  const int o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= co) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int sl = 0; sl < M5T_SLICES; sl++) {
-    s1 += part[((size_t)sl * co + o) * 2];
-    s2 += part[((size_t)sl * co + o) * 2 + 1];
-  }
-  const double mu = s1 / n;
-  double var = s2 / n - mu * mu;   // fp64 sums of fp32 values: the cancellation costs nothing an fp32 result can see
-  if (var < 0.0) var = 0.0;
-  stat[o * 4] = (float)mu;
-  stat[o * 4 + 1] = (float)(1.0 / sqrt(var + (double)eps));
-  const double m = (double)momentum;
-  new_rm[o] = (float)((1.0 - m) * (double)rm[o] + m * mu);
-  new_rv[o] = (float)((1.0 - m) * (double)rv[o] + m * var * (n / (n - 1.0)));
-}
+// (bn_stats_final_kernel then forms stat = [mean[co]; rstd[co]] and the new running statistics as torch does: the variance UNBIASED, T4)
 
 // y = gamma (z - mean) rstd + beta; a = maxpool4(relu(y)) over the first 4 Q positions; sel = which of the four won, 4 = shut by the ReLU
 __global__ __launch_bounds__(256) void m5t_apply_kernel(const float *__restrict__ z, const float *__restrict__ stat,
@@ -223,7 +191,7 @@ __global__ __launch_bounds__(256) void m5t_apply_kernel(const float *__restrict_
     const int q = (int)(idx % Q);
     const size_t r = idx / Q;
     const int o = (int)(r % co);
-    const float mu = stat[o * 4], rstd = stat[o * 4 + 1], g = gamma[o], be = beta[o];
+    const float mu = stat[o], rstd = stat[co + o], g = gamma[o], be = beta[o];
     const float *zr = z + r * P + 4 * q;
     float y[4];
 #pragma unroll
@@ -309,7 +277,7 @@ __global__ __launch_bounds__(256) void m5t_bstats_kernel(const float *__restrict
                                                          const float *__restrict__ da, const float *__restrict__ stat,
                                                          double *__restrict__ part, int B, int co, int P, int Q) {
   const int o = blockIdx.x, sl = blockIdx.y;
-  const float mu = stat[o * 4], rstd = stat[o * 4 + 1];
+  const float mu = stat[o], rstd = stat[co + o];
   double s1 = 0.0, s2 = 0.0;
   for (int b = sl; b < B; b += M5T_SLICES) {
     const size_t r = (size_t)b * co + o;
@@ -322,37 +290,23 @@ __global__ __launch_bounds__(256) void m5t_bstats_kernel(const float *__restrict
       }
     }
   }
-  block_sum2(s1, s2);
+  block_wave_sum2(s1, s2);
   if (threadIdx.x == 0) {
     part[((size_t)sl * co + o) * 2] = s1;
     part[((size_t)sl * co + o) * 2 + 1] = s2;
   }
 }
 
-// d bn.bias = sum dy, d bn.weight = sum dy xhat; stat[o][2..3] = their means over all n positions
-__global__ void m5t_bstats_final_kernel(const double *__restrict__ part, float *__restrict__ stat, float *__restrict__ dgamma,
-                                        float *__restrict__ dbeta, int co, double n) {
-  const int o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= co) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int sl = 0; sl < M5T_SLICES; sl++) {
-    s1 += part[((size_t)sl * co + o) * 2];
-    s2 += part[((size_t)sl * co + o) * 2 + 1];
-  }
-  dbeta[o] = (float)s1;
-  dgamma[o] = (float)s2;
-  stat[o * 4 + 2] = (float)(s1 / n);
-  stat[o * 4 + 3] = (float)(s2 / n);
-}
+// (bn_bstats_final_kernel: d bn.bias = sum dy, d bn.weight = sum dy xhat; mean2[o] = their means over all n positions)
 
 // dz = gamma rstd (dy - mean(dy) - xhat mean(dy xhat)) at EVERY position p < P: (T1) those at and beyond 4 Q have dy = 0 and still a
 // dz through the two mean terms.  part[slice][o] = (sum dz, 0): the conv bias gradient, zero in exact arithmetic, computed anyway.
 __global__ __launch_bounds__(256) void m5t_dz_kernel(const float *__restrict__ z, const unsigned char *__restrict__ sel,
                                                      const float *__restrict__ da, const float *__restrict__ stat,
-                                                     const float *__restrict__ gamma, float *__restrict__ dz,
+                                                     const double *__restrict__ mean2, const float *__restrict__ gamma, float *__restrict__ dz,
                                                      double *__restrict__ part, int B, int co, int P, int Q) {
   const int o = blockIdx.x, sl = blockIdx.y;
-  const float mu = stat[o * 4], rstd = stat[o * 4 + 1], m1 = stat[o * 4 + 2], m2 = stat[o * 4 + 3], gr = gamma[o] * rstd;
+  const float mu = stat[o], rstd = stat[co + o], m1 = (float)mean2[2 * o], m2 = (float)mean2[2 * o + 1], gr = gamma[o] * rstd;
   double s1 = 0.0, s2 = 0.0;
   for (int b = sl; b < B; b += M5T_SLICES) {
     const size_t r = (size_t)b * co + o;
@@ -366,21 +320,11 @@ __global__ __launch_bounds__(256) void m5t_dz_kernel(const float *__restrict__ z
       s1 += (double)v;
     }
   }
-  block_sum2(s1, s2);
+  block_wave_sum2(s1, s2);
   if (threadIdx.x == 0) {
     part[((size_t)sl * co + o) * 2] = s1;
     part[((size_t)sl * co + o) * 2 + 1] = 0.0;
   }
-}
-
-// out[e] = sum over the slices, in slice order, in fp64, rounded once.  T = double (pairs: `stride` = 2, first of each) or float
-template <typename T>
-__global__ __launch_bounds__(256) void m5t_slice_sum_kernel(const T *__restrict__ part, float *__restrict__ out, size_t n, int stride) {
-  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (e >= n) return;
-  double s = 0.0;
-  for (int sl = 0; sl < M5T_SLICES; sl++) s += (double)part[((size_t)sl * n + e) * stride];
-  out[e] = (float)s;
 }
 
 // split-K weight gradient: dW[o][c][t] = sum_{b,p} dz[b][o][p] in[b][c][p s + t] over EVERY p < P (T1).  One workgroup per (64 (c, t)
@@ -488,8 +432,8 @@ int launch_m5_train_fwd(ap_m5 *m, const float *blob, const float *x, float *logp
     m5t_conv_kernel<<<grid_for((size_t)B * ((P + 3) / 4) * co), 256, 0, st>>>(in, pk.wT[i], blob + pl.bb[i], z, B, pl.ci[i], co, pl.k[i],
                                                                            pl.s[i], pl.lin[i], P);
     m5t_stats_kernel<<<dim3(co, M5T_SLICES), 256, 0, st>>>(z, part, B, co, P);
-    m5t_stats_final_kernel<<<(co + 63) / 64, 64, 0, st>>>(part, blob + pl.brm[i], blob + pl.brv[i], stat, new_running + pl.rm[i],
-                                                        new_running + pl.rv[i], co, (double)B * P, m->eps, momentum);
+    bn_stats_final_kernel<M5T_SLICES><<<(co + 63) / 64, 64, 0, st>>>(part, blob + pl.brm[i], blob + pl.brv[i], stat, new_running + pl.rm[i],
+                                                                   new_running + pl.rv[i], co, (double)B * P, m->eps, momentum);
     m5t_apply_kernel<<<grid_for((size_t)B * co * Q), 256, 0, st>>>(z, stat, blob + pl.bg[i], blob + pl.bbe[i], a,
                                                                  keep ? (unsigned char *)(base + pl.sel[i]) : nullptr, B, co, P, Q);
     in = a;
@@ -509,7 +453,7 @@ int launch_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float
   float *da[2] = {(float *)(base + pl.da[0]), (float *)(base + pl.da[1])};
   float *feat = (float *)(base + pl.feat), *dlogit = (float *)(base + pl.dlogit), *dzb = (float *)(base + pl.dz);
   float *wpart = (float *)(base + pl.wpart);
-  double *part = (double *)(base + pl.part);
+  double *part = (double *)(base + pl.part), *mean2 = (double *)(base + pl.mean2);
   const int c2 = pl.co[3], n_out = m->n_output;
   m5t_head_kernel<<<B, 128, 0, st>>>((const float *)(base + pl.a[3]), blob + pl.bfw, blob + pl.bfb, nullptr, dlogp, feat, dlogit, da[0], c2,
                                     pl.Q[3], n_out);
@@ -520,14 +464,14 @@ int launch_m5_train_bwd(ap_m5 *m, const float *blob, const float *x, const float
     const int nW = co * ci * k;
     const float *z = (const float *)(base + pl.z[i]);
     const unsigned char *sel = (const unsigned char *)(base + pl.sel[i]);
-    float *stat = (float *)(base + pl.stat[i]);
+    const float *stat = (const float *)(base + pl.stat[i]);
     const float *in = i ? (const float *)(base + pl.a[i - 1]) : x;
     m5t_bstats_kernel<<<dim3(co, M5T_SLICES), 256, 0, st>>>(z, sel, da[cur], stat, part, B, co, P, Q);
-    m5t_bstats_final_kernel<<<(co + 63) / 64, 64, 0, st>>>(part, stat, grads + pl.gg[i], grads + pl.gbe[i], co, (double)B * P);
-    m5t_dz_kernel<<<dim3(co, M5T_SLICES), 256, 0, st>>>(z, sel, da[cur], stat, blob + pl.bg[i], dzb, part, B, co, P, Q);
-    m5t_slice_sum_kernel<double><<<(co + 255) / 256, 256, 0, st>>>(part, grads + pl.gb[i], (size_t)co, 2);
+    bn_bstats_final_kernel<M5T_SLICES><<<(co + 63) / 64, 64, 0, st>>>(part, mean2, grads + pl.gg[i], grads + pl.gbe[i], co, (double)B * P);
+    m5t_dz_kernel<<<dim3(co, M5T_SLICES), 256, 0, st>>>(z, sel, da[cur], stat, mean2, blob + pl.bg[i], dzb, part, B, co, P, Q);
+    slice_sum_kernel<double, M5T_SLICES><<<(co + 255) / 256, 256, 0, st>>>(part, grads + pl.gb[i], (size_t)co, /* slices: the template's */ 0, 2, 1.0f, 0);
     m5t_dw_kernel<<<dim3((ci * k + 63) / 64, (co + M5T_OB - 1) / M5T_OB, M5T_SLICES), 64 * M5T_DW_WAVES, 0, st>>>(dzb, in, wpart, B, ci, co, k, s, lin, P, nW);
-    m5t_slice_sum_kernel<float><<<(nW + 255) / 256, 256, 0, st>>>(wpart, grads + pl.gw[i], (size_t)nW, 1);
+    slice_sum_kernel<float, M5T_SLICES><<<(nW + 255) / 256, 256, 0, st>>>(wpart, grads + pl.gw[i], (size_t)nW, /* slices: the template's */ 0, 1, 1.0f, 0);
     if (i > 0) {
       m5t_din_kernel<<<grid_for((size_t)B * ci * lin), 256, 0, st>>>(dzb, blob + pl.bw[i], da[cur ^ 1], B, ci, co, k, s, lin, P);
       cur ^= 1;

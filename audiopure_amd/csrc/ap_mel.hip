@@ -133,13 +133,7 @@ __global__ __launch_bounds__(256) void mel_refmax_kernel(float *__restrict__ out
   float *p = out + (size_t)blockIdx.x * n;
   float mx = -INFINITY;
   for (int i = threadIdx.x; i < n; i += 256) mx = fmaxf(mx, p[i]);
-  red[threadIdx.x] = mx;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-    __syncthreads();
-  }
-  mx = red[0];
+  mx = block_tree<256>(mx, red, MaxOp{});
   for (int i = threadIdx.x; i < n; i += 256) p[i] = fmaxf(p[i] - mx, -80.0f);
 }
 

@@ -166,17 +166,6 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_step_kernel(const OptArgs a
   }
 }
 
-// sum over the workgroup in a fixed order (tree over LDS); the result is valid in lane 0
-__device__ __forceinline__ double block_sum(double s, double *red) {
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = OPT_THREADS / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 __global__ __launch_bounds__(OPT_THREADS) void optim_sqnorm_kernel(const SqnArgs a, int n_tensors, double *part) {
   __shared__ double red[OPT_THREADS];
   const uint32_t chunk = blockIdx.x;
@@ -199,7 +188,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_sqnorm_kernel(const SqnArgs
     done = nq << 2;
   }
   for (int i = done + threadIdx.x; i < len; i += OPT_THREADS) s += (double)g[i] * (double)g[i];
-  s = block_sum(s, red);
+  s = block_tree<OPT_THREADS>(s, red, SumOp{});
   if (threadIdx.x == 0) part[chunk] = s;
 }
 
@@ -207,7 +196,7 @@ __global__ __launch_bounds__(OPT_THREADS) void optim_sqnorm_final_kernel(const d
   __shared__ double red[OPT_THREADS];
   double s = 0.0;
   for (size_t i = threadIdx.x; i < n; i += OPT_THREADS) s += part[i];
-  s = block_sum(s, red);
+  s = block_tree<OPT_THREADS>(s, red, SumOp{});
   if (threadIdx.x == 0) out[0] = s;
 }
 

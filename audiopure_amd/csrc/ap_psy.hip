@@ -30,18 +30,6 @@ __device__ __forceinline__ float psd_db(double xr, double xi) {
   return fmaxf(p, -200.0f);                      // log10(0) = -inf -> -200, as clip(min=-200)
 }
 
-__device__ __forceinline__ float block_max(float v, float *red, int tid) {
-  red[tid] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] = fmaxf(red[tid], red[tid + s]);
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // PSD of one frame in dB [B][F][NB] and its maximum [B][F].  fp64 FFT: 2 x 32 KB data + 16 KB twiddles of LDS.
 __global__ __launch_bounds__(256) void psy_psd_kernel(const float *__restrict__ x, const double *__restrict__ tab,
                                                       float *__restrict__ psd, float *__restrict__ fmax_out, int F, int L,
@@ -67,7 +55,8 @@ __global__ __launch_bounds__(256) void psy_psd_kernel(const float *__restrict__ 
     out[k] = p;
     mx = fmaxf(mx, p);
   }
-  mx = block_max(mx, red, tid);
+  mx = block_tree<256>(mx, red, MaxOp{});
+  __syncthreads();
   if (tid == 0) fmax_out[(size_t)b * F + f] = mx;
 }
 
@@ -234,13 +223,8 @@ __global__ __launch_bounds__(256) void psy_loss_grad_kernel(const float *__restr
     }
     other[k] = v;
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) part[(size_t)b * F + f] = red[0];
+  acc = block_tree<256>(acc, red, SumOp{});
+  if (tid == 0) part[(size_t)b * F + f] = acc;
   float2 *R = fft2048(other, X, tw, tid);                       // X's storage is the scratch buffer now
   float *sc = scratch + ((size_t)b * F + f) * N;
   for (int n = tid; n < N; n += 256) {

@@ -7,18 +7,6 @@
 
 namespace ap {
 
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  const float r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // forward (groupnorm_kernel): xh = (x - mean) rstd; y0 = gamma xh + beta; y1 = y0 (1 + sc) + sh; y = act(y1).
 // backward: dxh = dy act'(y1) (1 + sc) gamma;  dx = rstd (dxh - mean(dxh) - xh mean(dxh xh))  over the group.
 __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const float *__restrict__ x, const float *__restrict__ gamma,
@@ -32,13 +20,15 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const float *__restr
   float *dxp = dx + off;
   float s = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) s += xp[i];
-  const float mean = block_sum256(s, red) / (float)n;
+  const float mean = block_tree<256>(s, red, SumOp{}) / (float)n;
+  __syncthreads();
   float v = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
     const float dlt = xp[i] - mean;
     v = __builtin_fmaf(dlt, dlt, v);
   }
-  const float rstd = 1.0f / sqrtf(block_sum256(v, red) / (float)n + eps);
+  const float rstd = 1.0f / sqrtf(block_tree<256>(v, red, SumOp{}) / (float)n + eps);
+  __syncthreads();
   auto dxh_of = [&](int i, float &xh) {
     const int c = g * cpg + i / HW;
     xh = (xp[i] - mean) * rstd;
@@ -48,14 +38,7 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const float *__restr
       y1 = y1 * sc + ss[(size_t)b * 2 * C + C + c];
       k *= sc;
     }
-    float d = dyp[i];
-    if (act == 2) {
-      const float sg = 1.0f / (1.0f + expf(-y1));
-      d *= sg * (1.0f + y1 * (1.0f - sg));
-    } else if (act == 1) {
-      d = y1 > 0.f ? d : 0.f;
-    }
-    return d * k;
+    return act_grad(dyp[i], y1, act) * k;
   };
   float s1 = 0.f, s2 = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -64,8 +47,10 @@ __global__ __launch_bounds__(256) void groupnorm_bwd_kernel(const float *__restr
     s1 += d;
     s2 = __builtin_fmaf(d, xh, s2);
   }
-  const float m1 = block_sum256(s1, red) / (float)n;
-  const float m2 = block_sum256(s2, red) / (float)n;
+  const float m1 = block_tree<256>(s1, red, SumOp{}) / (float)n;
+  __syncthreads();
+  const float m2 = block_tree<256>(s2, red, SumOp{}) / (float)n;
+  __syncthreads();
   for (int i = threadIdx.x; i < n; i += 256) {
     float xh;
     const float d = dxh_of(i, xh);

@@ -12,32 +12,6 @@
 namespace ap {
 namespace {
 
-// both sums of a 256-thread block at once, the tree in fp64 (the per-thread partials are fp32 sums of n / 256 terms)
-__device__ __forceinline__ void block_sum2(double a, double b, double *red, double &ra, double &rb) {
-  red[threadIdx.x] = a;
-  red[256 + threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      red[threadIdx.x] += red[threadIdx.x + o];
-      red[256 + threadIdx.x] += red[256 + threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  ra = red[0];
-  rb = red[256];
-  __syncthreads();
-}
-
-__device__ __forceinline__ float act_grad(float d, float y1, int act) {
-  if (act == 2) {
-    const float sg = 1.0f / (1.0f + expf(-y1));
-    return d * (sg * (1.0f + y1 * (1.0f - sg)));
-  }
-  if (act == 1) return y1 > 0.f ? d : 0.f;
-  return d;
-}
-
 // One workgroup per (sample, group) slab.  Notation of groupnorm_bwd_kernel (ap_unet_bwd.hip): xh = (x - mean) rstd, y0 = gamma xh +
 // beta, y1 = y0 (1 + sc) + sh, e = dy act'(y1).  Per channel c of the group, in channel order:
 //   S1 = sum_hw e, S2 = sum_hw e xh   ->   dss[b][c] = gamma S2 + beta S1 (= sum e y0), dss[b][C + c] = S1, sums[b][c] = (S1, S2)
@@ -47,6 +21,7 @@ __global__ __launch_bounds__(256) void groupnorm_train_bwd_kernel(const float *_
                                                                   const float *__restrict__ dy, float *__restrict__ dx,
                                                                   float *__restrict__ dss, float *__restrict__ sums, int C, int HW,
                                                                   int groups, float eps, int act) {
+  // two trees at once (block_tree2), in fp64: the per-thread partials are fp32 sums of n / 256 terms
   __shared__ double red[512];
   const int b = blockIdx.x / groups, g = blockIdx.x % groups, cpg = C / groups;
   const size_t n = (size_t)cpg * HW;
@@ -54,15 +29,19 @@ __global__ __launch_bounds__(256) void groupnorm_train_bwd_kernel(const float *_
   const float *xp = x + off, *dyp = dy + off;
   float s = 0.f;
   for (size_t i = threadIdx.x; i < n; i += 256) s += xp[i];
-  double t0, t1;
-  block_sum2((double)s, 0.0, red, t0, t1);
+  double t0 = (double)s, t1 = 0.0;
+  block_tree2<256>(t0, t1, red, SumOp{});
+  __syncthreads();
   const float mean = (float)(t0 / (double)n);
   float v = 0.f;
   for (size_t i = threadIdx.x; i < n; i += 256) {
     const float dlt = xp[i] - mean;
     v = __builtin_fmaf(dlt, dlt, v);
   }
-  block_sum2((double)v, 0.0, red, t0, t1);
+  t0 = (double)v;
+  t1 = 0.0;
+  block_tree2<256>(t0, t1, red, SumOp{});
+  __syncthreads();
   const float rstd = 1.0f / sqrtf((float)(t0 / (double)n) + eps);
 
   double a1 = 0.0, a2 = 0.0;                                  // sum_c k S1, sum_c k S2: the same value in every thread
@@ -78,8 +57,9 @@ __global__ __launch_bounds__(256) void groupnorm_train_bwd_kernel(const float *_
       s1 += e;
       s2 = __builtin_fmaf(e, xh, s2);
     }
-    double S1, S2;
-    block_sum2((double)s1, (double)s2, red, S1, S2);
+    double S1 = (double)s1, S2 = (double)s2;
+    block_tree2<256>(S1, S2, red, SumOp{});
+    __syncthreads();
     if (threadIdx.x == 0) {
       if (dss) {
         dss[(size_t)b * 2 * C + c] = (float)((double)gm * S2 + (double)bt * S1);
@@ -127,20 +107,6 @@ __global__ void groupnorm_param_kernel(const float *__restrict__ sums, const flo
   if (dbeta) dbeta[c] = (float)bsum;
 }
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&out)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; i++) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 // one thread per quad of a sample (blockIdx.y): elements 4 q .. 4 q + 3 below n; scalar accesses (n need not be a multiple of 4, so
 // a sample's base has no alignment beyond 4 bytes).  copy != 0 (p = 0): the bits of x.
 __global__ __launch_bounds__(256) void dropout_kernel(const float *__restrict__ x, float *__restrict__ y, int n, float p, float s,
@@ -168,8 +134,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float *__restrict__ 
 __global__ void silu_bwd_kernel(const float *__restrict__ x, const float *__restrict__ dy, float *__restrict__ dx, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float v = x[i], sg = 1.0f / (1.0f + expf(-v));
-  dx[i] = dy[i] * (sg * (1.0f + v * (1.0f - sg)));
+  dx[i] = act_grad(dy[i], x[i], 2);
 }
 
 __global__ void qsample_rows_kernel(const float *__restrict__ x0, const float *__restrict__ z, const float *__restrict__ a,

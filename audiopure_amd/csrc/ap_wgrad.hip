@@ -18,7 +18,7 @@ namespace ap {
 // t0 + floor4((k - taps/2) dil) and is WG_KC + 4 samples wide, the fragment read adds the remainder 0..3.
 // Wave (wm, wn) of the 2 x 2 owns rows [64 wm, 64 wm + 64) x columns [32 wn, 32 wn + 32): 2 x TAPS accumulator tiles.
 // K = B L is cut into chunks that never straddle a clip; slice z of the grid takes a contiguous run of chunks and writes its raw
-// partial sums to the workspace, wgrad_reduce_kernel adds the slices in slice order.
+// partial sums to the workspace, slice_sum_kernel adds the slices in slice order.
 // ---------------------------------------------------------------------------------------------
 constexpr int WG_KC = 32;                 // samples per staged chunk
 constexpr int WG_BM = 128, WG_BN = 64;    // tile of G per workgroup
@@ -191,17 +191,6 @@ __global__ __launch_bounds__(WG_NT) void wgrad_corr_kernel(WgradArgs a) {
   }
 }
 
-// G (+)= scale * (slice 0 + slice 1 + ...), in slice order
-__global__ void wgrad_reduce_kernel(const float *__restrict__ part, float *__restrict__ G, size_t total, int slices, float scale,
-                                    int accumulate) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
-  double s = 0.0;                                               // (the slices' own sums are the matrix pipe's fp32; their sum is not
-  for (int z = 0; z < slices; z++) s += (double)part[(size_t)z * total + idx];   // rounded again per slice)
-  const float v = (float)(s * (double)scale);
-  G[idx] = accumulate ? G[idx] + v : v;
-}
-
 static int wgrad_slices(int B, int M, int N, int L) {
   const long long tiles = (long long)((M + WG_BM - 1) / WG_BM) * ((N + WG_BN - 1) / WG_BN);
   const long long nchunk = (long long)B * ((L + WG_KC - 1) / WG_KC);
@@ -230,14 +219,9 @@ __global__ __launch_bounds__(256) void rowsum_kernel(const float *__restrict__ A
       s += (double)v;
     }
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+  s = block_tree<256>(s, red, SumOp{});
   if (threadIdx.x == 0) {
-    const OUT v = (OUT)((double)scale * red[0]);
+    const OUT v = (OUT)((double)scale * s);
     out[m] = accumulate ? out[m] + v : v;
   }
 }
@@ -250,7 +234,7 @@ __global__ __launch_bounds__(256) void rowsum_kernel(const float *__restrict__ A
 __global__ __launch_bounds__(256) void weight_norm_bwd_kernel(const float *__restrict__ dW, const float *__restrict__ v,
                                                               const float *__restrict__ g, float *__restrict__ dg,
                                                               float *__restrict__ dv, int cols) {
-  __shared__ double r1[256], r2[256];
+  __shared__ double red[512];
   const size_t row = (size_t)blockIdx.x * cols;
   double nn = 0.0, dot = 0.0;
   for (int i = threadIdx.x; i < cols; i += 256) {
@@ -258,18 +242,7 @@ __global__ __launch_bounds__(256) void weight_norm_bwd_kernel(const float *__res
     nn += x * x;
     dot += (double)dW[row + i] * x;
   }
-  r1[threadIdx.x] = nn;
-  r2[threadIdx.x] = dot;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) {
-      r1[threadIdx.x] += r1[threadIdx.x + w];
-      r2[threadIdx.x] += r2[threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-  nn = r1[0];
-  dot = r2[0];
+  block_tree2<256>(nn, dot, red, SumOp{});
   const double inv = nn > 0.0 ? 1.0 / sqrt(nn) : 0.0;           // (an all-zero v row has no direction: gradients 0, not NaN)
   if (threadIdx.x == 0) dg[blockIdx.x] = (float)(dot * inv);
   const double gs = (double)g[blockIdx.x] * inv, proj = dot * inv * inv;
@@ -332,7 +305,7 @@ __global__ __launch_bounds__(512) void embed_mlp_bwd_kernel(const float *__restr
   for (int o = wave; o < Emid; o += nw) {                       // wave per row
     double s = 0.0;
     for (int i = lane; i < Ein; i += 64) s += (double)w1[(size_t)o * Ein + i] * e0[i];
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+    s = wave_sum(s);
     if (lane == 0) {
       z1[o] = s + (double)b1[o];
       a1[o] = swish_d(s + (double)b1[o]);
@@ -342,7 +315,7 @@ __global__ __launch_bounds__(512) void embed_mlp_bwd_kernel(const float *__restr
   for (int o = wave; o < Eout; o += nw) {
     double s = 0.0;
     for (int i = lane; i < Emid; i += 64) s += (double)w2[(size_t)o * Emid + i] * a1[i];
-    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+    s = wave_sum(s);
     if (lane == 0) dz2[o] = demb[o] * swish_grad_d(s + (double)b2[o]);
   }
   __syncthreads();
@@ -402,7 +375,7 @@ extern "C" int ap_wgrad_corr(const float *P, const float *Q, const float *film, 
     else wgrad_launch_mode<1, false>(a, mode, grid, st);
   }
   const size_t total = (size_t)M * N * taps;
-  wgrad_reduce_kernel<<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a.part, G, total, a.slices, p_scale, accumulate);
+  slice_sum_kernel<float><<<(unsigned)((total + 255) / 256), 256, 0, st>>>(a.part, G, total, a.slices, 1, p_scale, accumulate);
   AP_HIP(hipGetLastError());
   return 0;
 }

@@ -9,7 +9,11 @@ before comparing: comment lines, `.file` / `.ident` lines and the `__hip_cuid_<h
 Prints identical/different per file and exits 1 if any file differs -- the check of a refactor that must not move an instruction.
 --by-symbol: a file that differs line by line still counts as identical if its symbols are the same set and every symbol's text
 (function, kernel descriptor, metadata entry; the function's running number taken out of local labels) is the same -- a reordered
-host launcher changes the order in which template instantiations are emitted and nothing else.
+host launcher changes the order in which template instantiations are emitted and nothing else.  By symbol, three more things that
+move with a symbol's position and not with its code are left out of its text: the remark behind a local label (`; in Loop: ...`,
+padded to a column by the label's width), bare `.text` lines (there or not by whether a template's own section follows), and the
+file's tail (`.p2alignl` padding, `.AMDGPU.gpr_maximums`, the metadata's `amdhsa.target` / `amdhsa.version`), which is compared
+under the key "" and not as part of whichever symbol happens to come last.  Every differing symbol is listed.
 """
 import os
 import re
@@ -41,13 +45,14 @@ def device_asm(tree, name, tools):
 
 
 _ANNOUNCE = re.compile(r"^\s*(?:\.(?:globl|weak|protected|hidden)\s+([^\s,]+)|\.section\s+\.text\.([^\s,]+),)")
-_LOCAL = re.compile(r"(\.L|Header=)(BB|func_begin|func_end|tmp)\d+")
+_LOCAL = re.compile(r"(\.L|Header=|Loop )(BB|func_begin|func_end|tmp)\d+")   # "Loop ": the `; Parent Loop BB<n>_<k>` remark behind a label
 
 
 def by_symbol(lines):
     """{symbol: its lines}: function text + kernel descriptor (from the first directive that names the symbol to the next symbol's)
     and, under "meta:<symbol>", its entry of the metadata's kernel list; "" holds what belongs to no symbol.  The per-function
-    number in local labels (.LBB<n>_<k>, .Lfunc_end<n>) is dropped: it is the function's position in the file."""
+    number in local labels (.LBB<n>_<k>, .Lfunc_end<n>) is dropped: it is the function's position in the file; so are a label's
+    trailing remark (padded by that number's width) and bare `.text` lines."""
     out, key, meta = {}, "", False
     for line in lines:
         if ".amdgpu_metadata" in line:
@@ -58,10 +63,17 @@ def by_symbol(lines):
             m = _ANNOUNCE.match(line)
             if m:
                 key = m.group(1) or m.group(2)
+        if (meta and line.startswith("amdhsa.")) or ".p2alignl" in line or ".AMDGPU.gpr_maximums" in line:
+            key = ""                                    # the file's own tail, not the last symbol's
         if meta and isinstance(key, tuple) and line.startswith("    .name:"):
             out["meta:" + line.split()[1]] = out.pop(key)
             key = "meta:" + line.split()[1]
-        out.setdefault(key, []).append(_LOCAL.sub(r"\1\2", line))
+        if line.strip() == ".text":                     # switches back from a template's own section: there or not by what follows
+            continue
+        line = _LOCAL.sub(r"\1\2", line)
+        if line.startswith(".L"):                       # a label's remark is padded to a column that moves with the number's width
+            line = line.split(";")[0].rstrip()
+        out.setdefault(key, []).append(line)
     return out
 
 
@@ -80,7 +92,7 @@ def main():
         if not same and sym:                            # the same symbols with the same text, emitted in another order
             sa, sb = by_symbol(xa), by_symbol(xb)
             diff = sorted(k for k in set(sa) | set(sb) if sa.get(k) != sb.get(k))
-            same, note = not diff, f"  ({len(sa)} symbols, order differs)" if not diff else "  differing symbols: " + " ".join(map(str, diff[:6]))
+            same, note = not diff, f"  ({len(sa)} symbols, order differs)" if not diff else "  differing symbols:" + "".join("\n    " + str(k) for k in diff)
         bad += not same
         print(f"{'tools  ' if tools else 'product'} {name:28s} {len(xa):7d} lines  {'identical' if same else 'DIFFERENT'}{note}")
     print(f"{len(jobs) - bad} of {len(jobs)} identical")
